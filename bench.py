@@ -21,9 +21,16 @@ proofs / wall time (max over ranks), n_gpus = devices actually used:
     device 0 (pipelines sharing one copy of the base tables) and marks the line
     "rehearsal": true -- a check of the multi-device code path, not a scaling number.
 Every timed proof and every batch proof is compared with a separately computed proof of
-the same witness at the same r, s.  Extra fields: latency, per-stage ms, config-1 kernels
-(G1 MSM 2^20 Mpts/s, Fr NTT 2^20 / 2^23), roofline of the bucket-accumulate kernel (HIP
-events), and the C++ CPU restatement (oracle/cpu) timed on this host as cpu_baseline.
+the same witness at the same r, s.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the result line with what those steps themselves yield: proofs/s, ms_per_step, per-stage ms
+and the roofline of the bucket-accumulate launches of the timed proofs (HIP events).  `--full` adds
+every measurement that takes runs of its own: two proofs in flight, 1-proof latency (staged and
+from a host witness), the PCIe-inclusive batch, the sustained loop, the config-1 kernels (G1 MSM
+2^20 Mpts/s, Fr NTT 2^20 / 2^23), the all-uniform-witness bound, and the C++ CPU restatement
+(oracle/cpu) timed on this host as cpu_baseline.  `--dump-outputs DIR` writes the proof and the
+public signals of the last timed step as DIR/proof.npy and DIR/public_signals.npy.
 """
 import argparse
 import ctypes
@@ -362,6 +369,8 @@ def run_split(args, rank, world, local):
         del full
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [res])
     out = {
         "metric": "Groth16 proofs/sec (node) + 1-proof latency; configs[4] single proof split by point range",
         "value": round(args.steps / elapsed, 4), "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
@@ -650,12 +659,31 @@ def sustained_line(args, prover, ndev, nw, refs, dist, sync, on_devices, r_fix, 
             "note": "staged loop, one proof at a time per device, for >= %.0f s; every proof checked" % args.sustain_s}
 
 
+def dump_outputs(path, results):
+    """--dump-outputs: what the timed path returned in its last step, one row per device: `results` holds a
+    ((a, b, c), public signals) tuple as Prover.prove_staged_raw returns it.  Every field element (< 2^256)
+    becomes 8 little-endian 32-bit limbs, each exact in float64, so two builds compare output for output.
+      proof.npy           float64 [devices, 8, 8]: ax, ay, bx0, bx1, by0, by1, cx, cy
+      public_signals.npy  float64 [devices, n_public, 8]"""
+    import numpy as np
+
+    def limbs(x):
+        return [(x >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
+    proofs, pubs = [], []
+    for (a, b, c), pub in results:
+        proofs.append([limbs(v) for v in (a[0], a[1], b[0][0], b[0][1], b[1][0], b[1][1], c[0], c[1])])
+        pubs.append([limbs(v) for v in pub])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "proof.npy"), np.array(proofs, dtype=np.float64).reshape(len(results), 8, 8))
+    np.save(os.path.join(path, "public_signals.npy"), np.array(pubs, dtype=np.float64).reshape(len(results), -1, 8))
+
+
 def compact_line(out):
     """The contract line the driver keeps (its record holds the last 8 KB of stdout):
     the metric's two halves (proofs/s and 1-proof latency), the sustained and batch rates, the headline
     roofline and cpu_baseline, and the configs[1] kernel numbers.  Everything else is in the
     {"bench_detail": ...} line printed just before it."""
-    keep = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "latency_ms", "latency_ms_staged",
+    keep = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "full", "latency_ms", "latency_ms_staged",
             "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "value_note", "all_proofs_ok",
             "rehearsal"]
     c = {k: out[k] for k in keep if k in out}
@@ -707,6 +735,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--witnesses", type=int, default=4, help="distinct staged witnesses per rank (cycled)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement (two proofs in flight, 1-proof "
+                         "latency, PCIe-inclusive batch, sustained loop, config-1 kernels, all-uniform-witness "
+                         "bound, CPU baseline); the options below that trim them apply only with --full.  Without "
+                         "it the run sets up, warms up, times --steps proofs and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the proof and the public signals the last timed step "
+                         "returned (one row per device) as DIR/proof.npy and DIR/public_signals.npy (float64, "
+                         "8 little-endian 32-bit limbs per field element); inputs are seeded, so equal arguments "
+                         "give equal files")
     ap.add_argument("--cpu-baseline", choices=["full", "none"], default="full")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every usable host core (nproc, cgroup quota)")
     ap.add_argument("--no-kernels", action="store_true")
@@ -738,6 +776,9 @@ def main():
                     help="--gpus N without torchrun on fewer GPUs: N logical devices on one GPU (code-path check; "
                          "the line says \"rehearsal\": true and is not a scaling number)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        log("bench.py: --steps must be >= 1 and --warmup >= 0")
+        sys.exit(2)
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -896,11 +937,13 @@ def main():
 
     launches = prover.launch_stats()
     prover.instrument(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [per_dev[d][args.steps - 1] for d in range(ndev)])
     # the same staged loop with two proofs in flight per device (the next proof's first kernels fill the
     # previous one's finishing tail: +1.3-2.2 % in round 3, profiles/inflight_hwq_r03.txt), every proof
     # checked; reported beside the headline, not as `value` (its launches overlap: no per-launch time)
     two = None
-    if int(os.environ.get("ZKP_INFLIGHT", "1")) >= 2 and inflight == 1:
+    if args.full and int(os.environ.get("ZKP_INFLIGHT", "1")) >= 2 and inflight == 1:
         if dist:
             dist.barrier()
         sync()
@@ -912,36 +955,55 @@ def main():
         two = {"proofs_per_s": round(args.steps * ndev / el2, 4), "ms_per_proof": round(el2 / args.steps * 1e3, 3),
                "all_proofs_ok": not bad2, "in_flight_per_device": 2}
         mismatch += [("two in flight", d, i) for d, i in bad2]
-    # 1-proof latency, witness in HBM: one staged proof at a time (median of 5)
-    lat_st = []
-    for i in range(5):
-        t0 = time.perf_counter()
-        prover.prove_staged_raw(i % nw, R_FIX, S_FIX, dev_index=0)
-        lat_st.append((time.perf_counter() - t0) * 1e3)
-    staged_latency_ms = sorted(lat_st)[2]
-    # 1-proof latency from a HOST witness (the reference call: zkp.ts:94, 5_gen_proof.sh:8): upload
-    # through the pinned slot + proof + assembly, one proof at a time (median of 5, each checked)
-    lat, up_ms, up_mb = [], [], []
-    for i in range(5):
-        t0 = time.perf_counter()
-        pr = prover.prove_raw(wit[i % nw], R_FIX, S_FIX)
-        lat.append((time.perf_counter() - t0) * 1e3)
-        tm = prover.timings()
-        up_ms.append(tm["wtns_h2d"])
-        up_mb.append(tm["wtns_pcie_mb"])
-        if pr != refs[i % nw]:
-            mismatch.append(("host-witness latency proof", i))
-    first_host_ms = lat[0]  # the process's first host-witness proof (upload slot 0 exists from load on)
-    lat.sort()
-    up_ms.sort()
-    pcie_latency_ms, upload_ms = lat[len(lat) // 2], up_ms[len(up_ms) // 2]
+    latency = None
+    if args.full:
+        # 1-proof latency, witness in HBM: one staged proof at a time (median of 5)
+        lat_st = []
+        for i in range(5):
+            t0 = time.perf_counter()
+            prover.prove_staged_raw(i % nw, R_FIX, S_FIX, dev_index=0)
+            lat_st.append((time.perf_counter() - t0) * 1e3)
+        staged_latency_ms = sorted(lat_st)[2]
+        # 1-proof latency from a HOST witness (the reference call: zkp.ts:94, 5_gen_proof.sh:8): upload
+        # through the pinned slot + proof + assembly, one proof at a time (median of 5, each checked)
+        lat, up_ms, up_mb = [], [], []
+        for i in range(5):
+            t0 = time.perf_counter()
+            pr = prover.prove_raw(wit[i % nw], R_FIX, S_FIX)
+            lat.append((time.perf_counter() - t0) * 1e3)
+            tm = prover.timings()
+            up_ms.append(tm["wtns_h2d"])
+            up_mb.append(tm["wtns_pcie_mb"])
+            if pr != refs[i % nw]:
+                mismatch.append(("host-witness latency proof", i))
+        first_host_ms = lat[0]  # the process's first host-witness proof (upload slot 0 exists from load on)
+        lat.sort()
+        up_ms.sort()
+        pcie_latency_ms, upload_ms = lat[len(lat) // 2], up_ms[len(up_ms) // 2]
+        wit_bytes = circ.n_vars * 32
+        latency = {
+            "latency_ms": round(pcie_latency_ms, 3),
+            "latency_ms_staged": round(staged_latency_ms, 3),
+            "latency_ms_first_host_proof": round(first_host_ms, 3),
+            "latency_note": "latency_ms = one proof from a host witness (pinned-slot upload + proof + assembly), "
+                            "median of 5; latency_ms_staged = one staged proof at a time (witness already in HBM), "
+                            "median of 5; the timed loop keeps staged_in_flight_per_device proofs in flight per GPU",
+            "witness_upload": {"ms": round(upload_ms, 3), "witness_bytes": wit_bytes,
+                               "pcie_bytes": int(max(up_mb) * 1e6),
+                               "witness_GBps": round(wit_bytes / (upload_ms * 1e-3) / 1e9, 1) if upload_ms > 0 else None,
+                               "host_encode_threads": 16,
+                               "note": "compact transfer: 16 host threads encode 64K-signal chunks (0/1 values as "
+                                       "metadata bits, other values < 2^32 as one word) into pinned memory with "
+                                       "non-temporal stores, each chunk's DMA on one of 4 copy queues as soon as it "
+                                       "is encoded, one kernel expands them in HBM; ms = pageable witness -> 32-B "
+                                       "layout in HBM"}}
 
     batch = None
-    if args.batch > 0:
+    if args.full and args.batch > 0:
         batch = batch_pcie_inclusive(args, circ, prover, wit, refs, rank, world, ndev, dist, sync, R_FIX, S_FIX)
 
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         sustained = sustained_line(args, prover, ndev, nw, refs, dist, sync, on_devices, R_FIX, S_FIX)
 
     if rank != 0:
@@ -953,7 +1015,6 @@ def main():
     peak, peak_src = load_peak()
     traffic = load_traffic()
     roofline, acc_lines = accumulate_rooflines(launches, peak, peak_src, traffic)
-    wit_bytes = circ.n_vars * 32
 
     out = {
         "metric": "Groth16 proofs/sec (node) + 1-proof latency, Venmo circuit; G1 MSM Mpts/s",
@@ -963,23 +1024,12 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 3),
-        "latency_ms": round(pcie_latency_ms, 3),
-        "latency_ms_staged": round(staged_latency_ms, 3),
-        "latency_ms_first_host_proof": round(first_host_ms, 3),
+        "full": args.full,
         "staged_in_flight_per_device": inflight,
         "staged_two_in_flight": two,
-        "latency_note": "latency_ms = one proof from a host witness (pinned-slot upload + proof + assembly), "
-                        "median of 5; latency_ms_staged = one staged proof at a time (witness already in HBM), "
-                        "median of 5; the timed loop keeps staged_in_flight_per_device proofs in flight per GPU",
-        "witness_upload": {"ms": round(upload_ms, 3), "witness_bytes": wit_bytes,
-                           "pcie_bytes": int(max(up_mb) * 1e6),
-                           "witness_GBps": round(wit_bytes / (upload_ms * 1e-3) / 1e9, 1) if upload_ms > 0 else None,
-                           "host_encode_threads": 16,
-                           "note": "compact transfer: 16 host threads encode 64K-signal chunks (0/1 values as "
-                                   "metadata bits, other values < 2^32 as one word) into pinned memory with "
-                                   "non-temporal stores, each chunk's DMA on one of 4 copy queues as soon as it is "
-                                   "encoded, one kernel expands them in HBM; ms = pageable witness -> 32-B layout "
-                                   "in HBM"},
+    }
+    out.update(latency or {})
+    out.update({
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1000,7 +1050,10 @@ def main():
         "sustained": sustained,
         "roofline": roofline,
         "roofline_launches": acc_lines,
-    }
+    })
+    if not args.full:  # the lines only --full measures are left out, not reported as null
+        for k in ("staged_two_in_flight", "batch_pcie_inclusive", "sustained"):
+            del out[k]
 
     if rehearsal:
         out["rehearsal"] = True
@@ -1011,7 +1064,7 @@ def main():
     msm_case = None
     if batch:
         batch["vs_staged_headline"] = round(batch["proofs_per_s"] / value, 4)
-    if not args.no_kernels:
+    if args.full and not args.no_kernels:
         kb, kst, msm_case = kernel_benches(devices[0])
         out["kernels_config1"] = kb
         if peak and kst["ms_accumulate"] > 0:
@@ -1020,11 +1073,11 @@ def main():
             roofline["isolated_launch"] = {"workload": "configs[1] G1 MSM 2^20 accumulate, kernel alone",
                                            "mixed_adds": kst["mixed_adds"], "avg_launch_ms": round(kst["ms_accumulate"], 4),
                                            "achieved": round(iso, 3), "frac": round(iso / peak, 4)}
-    if args.bool0_line and args.bool_pct != 0 and args.scale == 1.0:
+    if args.full and args.bool0_line and args.bool_pct != 0 and args.scale == 1.0:
         prover.close()  # its HBM goes to the all-uniform line's prover
         out["all_uniform_witness"] = bool0_line(args, devices[0], R_FIX, S_FIX)
 
-    if args.cpu_baseline == "full":
+    if args.full and args.cpu_baseline == "full":
         out["cpu_baseline"] = cpu_baseline(args, zk, wit[0], results[0][0], R_FIX, S_FIX, msm_case)
     if sustained:
         sustained["vs_value"] = round(sustained["proofs_per_s"] / value, 4)
