@@ -89,12 +89,12 @@ def prove(z: ZKey, w, r: int, s: int):
 
 
 def split_range(n: int, part: int, nparts: int, balance: bool = False):
-    """[lo, hi) of slice `part` of n items in nparts contiguous ranges (as prover.hip split_range);
+    """[lo, hi) of slice `part` of n items in nparts contiguous ranges (as device_pipeline.hip split_range);
     balance (ZKP_SPLIT_BALANCE=1 there): for nparts > 3, parts 0..2 (the quotient-vector owners)
     weigh max(1, 11 - nparts) and the others 11."""
     if not balance or nparts <= 3:
         return n * part // nparts, n * (part + 1) // nparts
-    wq = max(1, 11 - nparts)  # see prover.hip split_range
+    wq = max(1, 11 - nparts)  # see device_pipeline.hip split_range
     cum = lambda k: wq * min(k, 3) + 11 * max(k - 3, 0)  # noqa: E731
     return n * cum(part) // cum(nparts), n * cum(part + 1) // cum(nparts)
 

@@ -1,4 +1,4 @@
-"""The compact witness transfer (prover.hip DevicePipeline::upload + qap.hip k_witness_unpack): the
+"""The compact witness transfer (device_pipeline.hip DevicePipeline::upload + qap.hip k_witness_unpack): the
 host sends each block of 64 signals as its 0 / 1 values in the block metadata, its values >= 2^32
 (32 B) and the low words of the others; the device expands them.  A proof from a host witness must equal oracle/cpu's proof of the same
 witness at the same r, s, whatever the mix of small and large values and wherever they sit in their
@@ -129,7 +129,7 @@ def test_batch_of_mixes_on_inflight_pipelines(setup, monkeypatch):
 @pytest.mark.parametrize("kind", ["bits", "all_large"])
 @pytest.mark.parametrize("wsel", ["first", "second", "auto"])
 def test_witness_configurations_equal_oracle(setup, kind, wsel, monkeypatch):
-    """Both resident witness-MSM configurations (window bits c and c + 2, prover.hip pick_wset): a
+    """Both resident witness-MSM configurations (window bits c and c + 2, device_pipeline.hpp pick_wset): a
     proof equals oracle/cpu's whichever one it takes -- forced first or second, or chosen per proof by
     the witness's share of values >= 2^32 (auto: the uniform witness takes the second, the 0/1-heavy
     one the first), from a host witness and from a staged one."""

@@ -213,11 +213,7 @@ MsmBases::MsmBases(Curve curve, size_t n, int c, int depth) : curve_(curve), n_(
   if ((size_t)depth * std::max<size_t>(n, 1) >= (size_t(1) << 31))
     throw std::runtime_error("MsmBases: depth * n must stay below 2^31 (31-bit base indices)");
   bytes_ = bytes_for(curve, n, depth);
-  HIPX(hipMalloc(&d_, bytes_));
-}
-
-MsmBases::~MsmBases() {
-  if (d_) (void)hipFree(d_);
+  d_ = DevBuf<>(bytes_ / 4);
 }
 
 void MsmBases::extend(hipStream_t st) {
@@ -233,10 +229,8 @@ void MsmBases::extend(hipStream_t st) {
 
 // ------------------------------------------------------------------ MsmPlan
 
-MsmPlan::MsmPlan(Init, size_t max_n, const MsmParams& prm, hipStream_t stream)
-    : prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream) {}
-
-MsmPlan::MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream) : MsmPlan(Init{}, max_n, prm, stream) {
+MsmPlan::MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream)
+    : prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream) {
   if (prm_.c < MsmParams::MIN_C || prm_.c > MsmParams::MAX_C || prm_.windows > HS_STAGE / HS_TPB)
     throw std::invalid_argument("MSM: window bits outside the plan's range");
   if (max_n_ * prm_.depth >= (size_t(1) << 31)) throw std::runtime_error("MSM size too large for 31-bit base indices");
@@ -245,20 +239,18 @@ MsmPlan::MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream) : MsmPl
   if (max_entries_ >= 0xffffffffull) throw std::runtime_error("MSM size too large for 32-bit entry indices");
   max_tasks_ = (max_entries_ + prm_.S - 1) / prm_.S + nbuckets_;
   merge_levels_ = msm_merge_levels(max_n_, prm_);
-  HIPX(hipMalloc(&vals_sorted_, max_entries_ * 4));
-  HIPX(hipMalloc(&bstart_, (nbuckets_ + 1) * 4));
-  HIPX(hipMalloc(&bend_, (nbuckets_ + 1) * 4));
-  HIPX(hipMalloc(&cnt_, (nbuckets_ + 1) * 4));
-  HIPX(hipMalloc(&off_task_, (nbuckets_ + 1) * 4));
-  HIPX(hipMalloc(&perm_, max_tasks_ * 4));
+  vals_sorted_ = DevBuf<>(max_entries_);
+  bstart_ = DevBuf<>(nbuckets_ + 1);
+  bend_ = DevBuf<>(nbuckets_ + 1);
+  cnt_ = DevBuf<>(nbuckets_ + 1);
+  off_task_ = DevBuf<>(nbuckets_ + 1);
+  perm_ = DevBuf<>(max_tasks_);
   const size_t ntl = (size_t)(prm_.S + 1) * grid_for(max_tasks_);
-  HIPX(hipMalloc(&tl_hist_, ntl * 4));
-  HIPX(hipMalloc(&tl_off_, ntl * 4));
-  off_lvl_.assign(merge_levels_, nullptr);
+  tl_hist_ = DevBuf<>(ntl);
+  tl_off_ = DevBuf<>(ntl);
   if (merge_levels_ > 0) {
-    HIPX(hipMalloc(&lvl_all_, (size_t)merge_levels_ * (nbuckets_ + 1) * 4));
-    for (int l = 0; l < merge_levels_; ++l) off_lvl_[l] = lvl_all_ + (size_t)l * (nbuckets_ + 1);
-    HIPX(hipMalloc(&lvl_tsum_, (size_t)merge_levels_ * scan_tiles_for(nbuckets_ + 1) * 4));
+    lvl_all_ = DevBuf<>((size_t)merge_levels_ * (nbuckets_ + 1));
+    lvl_tsum_ = DevBuf<>((size_t)merge_levels_ * scan_tiles_for(nbuckets_ + 1));
   }
   // bucket-key bits kb = b1 (bin) + b2 (sub-bin) + b3 (bucket in sub-bin): b3 = 5 for the one-
   // workgroup-per-sub-bin pass C (k_hs_fine), up to 9 (tiled pass C) when kb > 23 (c > 20 with
@@ -278,32 +270,22 @@ MsmPlan::MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream) : MsmPl
   const uint32_t nq = hs_nbins_ << hs_b2_;
   hs_max_tiles3_ = (uint32_t)((max_entries_ + HS_TILE - 1) / HS_TILE + nq);
   const size_t nh3 = ((size_t)hs_max_tiles3_ << hs_b3_) + 1;
-  HIPX(hipMalloc(&hs_toff3_, ((size_t)nq + 1) * 4));
-  HIPX(hipMalloc(&hs_hist3_, nh3 * 4));
-  HIPX(hipMalloc(&hs_off3_, nh3 * 4));
+  hs_toff3_ = DevBuf<>((size_t)nq + 1);
+  hs_hist3_ = DevBuf<>(nh3);
+  hs_off3_ = DevBuf<>(nh3);
   const size_t nh = (size_t)hs_nbins_ * hs_nblk_, nh2 = (size_t)hs_max_tiles_ << hs_b2_;
-  HIPX(hipMalloc(&hs_hist_, nh * 4));
-  HIPX(hipMalloc(&hs_blkoff_, nh * 4));
-  HIPX(hipMalloc(&hs_binbase_, (hs_nbins_ + 1) * 4));
-  HIPX(hipMalloc(&hs_toff_, (hs_nbins_ + 1) * 4));
-  HIPX(hipMalloc(&hs_hist2_, nh2 * 4));
-  HIPX(hipMalloc(&hs_off2_, nh2 * 4));
-  HIPX(hipMalloc(&hs_subbase_, ((size_t)nq + 1) * 4));
-  HIPX(hipMalloc(&hs_ent_a_, max_entries_ * 8));
-  HIPX(hipMalloc(&hs_ent_b_, max_entries_ * 8));
+  hs_hist_ = DevBuf<>(nh);
+  hs_blkoff_ = DevBuf<>(nh);
+  hs_binbase_ = DevBuf<>(hs_nbins_ + 1);
+  hs_toff_ = DevBuf<>(hs_nbins_ + 1);
+  hs_hist2_ = DevBuf<>(nh2);
+  hs_off2_ = DevBuf<>(nh2);
+  hs_subbase_ = DevBuf<>((size_t)nq + 1);
+  hs_ent_a_ = DevBuf<uint2>(max_entries_);
+  hs_ent_b_ = DevBuf<uint2>(max_entries_);
   const size_t scan_n = std::max(std::max(std::max(nbuckets_ + 1, nh3), std::max(nh2, ntl)), nh);
-  HIPX(hipMalloc(&tsum_, (scan_tiles_for(scan_n) + 1) * 4));
-  HIPX(hipEventCreateWithFlags(&ready_, hipEventDisableTiming));
-}
-
-MsmPlan::~MsmPlan() {
-  if (ready_) (void)hipEventDestroy(ready_);
-  for (void* p : {(void*)vals_sorted_, (void*)bstart_, (void*)bend_, (void*)cnt_, (void*)off_task_, (void*)hs_hist_,
-                  (void*)hs_blkoff_, (void*)hs_binbase_, (void*)hs_toff_, (void*)hs_hist2_,
-                  (void*)hs_off2_, (void*)hs_subbase_, hs_ent_a_, hs_ent_b_, (void*)tsum_, (void*)perm_,
-                  (void*)tl_hist_, (void*)tl_off_, (void*)hs_toff3_, (void*)hs_hist3_, (void*)hs_off3_,
-                  (void*)lvl_all_, (void*)lvl_tsum_})
-    if (p) (void)hipFree(p);
+  tsum_ = DevBuf<>(scan_tiles_for(scan_n) + 1);
+  ready_ = Event(false);
 }
 
 void MsmPlan::build(const uint32_t* scalars, size_t n) {
@@ -329,8 +311,8 @@ void MsmPlan::build(const uint32_t* scalars, size_t n) {
     const int k = hs_k_;
     const uint32_t nblk = (uint32_t)((n + k * HS_TPB - 1) / (k * HS_TPB)), nsub = 1u << hs_b2_;
     const int sh1 = hs_b2_ + hs_b3_;
-    uint2* ea = static_cast<uint2*>(hs_ent_a_);
-    uint2* eb = static_cast<uint2*>(hs_ent_b_);
+    uint2* ea = hs_ent_a_;
+    uint2* eb = hs_ent_b_;
     // A: digits -> bins
     auto count1 = k == 4 ? k_hs_count1<4> : (k == 2 ? k_hs_count1<2> : k_hs_count1<1>);
     hipLaunchKernelGGL(count1, dim3(nblk), dim3(HS_TPB), 0, st, scalars, (uint32_t)n, prm_.c, (int)W, prm_.depth, sh1,
@@ -402,42 +384,25 @@ void MsmPlan::build(const uint32_t* scalars, size_t n) {
 
 // ------------------------------------------------------------------ MsmEngine
 
-MsmEngine::MsmEngine(Init, Curve curve, const MsmParams& prm, size_t max_n, hipStream_t stream)
-    : curve_(curve), prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream) {}
-
 MsmEngine::MsmEngine(Curve curve, const MsmParams& prm, size_t max_n, hipStream_t stream)
-    : MsmEngine(Init{}, curve, prm, max_n, stream) {
+    : curve_(curve), prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream) {
   fwords_ = curve_fwords(curve);
   const size_t half = prm_.half();
   nbuckets_ = prm_.buckets();
   max_tasks_ = (max_n_ * prm_.windows + prm_.S - 1) / prm_.S + nbuckets_;
   const size_t xyzz_words = 4 * (size_t)fwords_;
-  HIPX(hipMalloc(&part_a_, max_tasks_ * xyzz_words * 4));
-  HIPX(hipMalloc(&part_b_, max_tasks_ * xyzz_words * 4));
-  HIPX(hipMalloc(&buckets_, nbuckets_ * xyzz_words * 4));
+  part_a_ = DevBuf<>(max_tasks_ * xyzz_words);
+  part_b_ = DevBuf<>(max_tasks_ * xyzz_words);
+  buckets_ = DevBuf<>(nbuckets_ * xyzz_words);
   const size_t nseg = (size_t)prm_.groups * (half / prm_.M);
-  HIPX(hipMalloc(&seg_s_, nseg * xyzz_words * 4));
-  HIPX(hipMalloc(&seg_t_, nseg * xyzz_words * 4));
+  seg_s_ = DevBuf<>(nseg * xyzz_words);
+  seg_t_ = DevBuf<>(nseg * xyzz_words);
   const size_t n1 = (size_t)prm_.groups * prm_.K() *
                     std::max(((half / prm_.M) + 2 * msmk::TREE_CHAIN_FAN - 1) / (2 * msmk::TREE_CHAIN_FAN),
                              ((half / prm_.M) + 2 * msmk::TREE_TPB - 1) / (2 * msmk::TREE_TPB));
-  for (int i = 0; i < 2; ++i) HIPX(hipMalloc(&sub_[i], n1 * xyzz_words * 4));
-  for (auto& e : ev_) {
-    HIPX(hipEventCreate(&e[0]));
-    HIPX(hipEventCreate(&e[1]));
-  }
-  HIPX(hipHostMalloc(&h_counts_, 2 * MAX_PENDING * 4, hipHostMallocDefault));
-}
-
-MsmEngine::~MsmEngine() {
-  for (auto& e : ev_) {
-    if (e[0]) (void)hipEventDestroy(e[0]);
-    if (e[1]) (void)hipEventDestroy(e[1]);
-  }
-  if (h_counts_) (void)hipHostFree(h_counts_);
-  for (void* p : {(void*)part_a_, (void*)part_b_, (void*)buckets_, (void*)seg_s_, (void*)seg_t_, (void*)sub_[0],
-                  (void*)sub_[1]})
-    if (p) (void)hipFree(p);
+  for (int i = 0; i < 2; ++i) sub_[i] = DevBuf<>(n1 * xyzz_words);
+  for (auto& e : ev_) e[0] = Event(true), e[1] = Event(true);
+  h_counts_ = PinnedBuf<uint32_t>(2 * MAX_PENDING);
 }
 
 void MsmEngine::collect(Stats& s) {
@@ -464,7 +429,7 @@ void MsmEngine::accumulate(const MsmPlan& plan, const MsmBases& bases) {
   if (plan.n() > max_n_) throw std::runtime_error("MSM: n exceeds engine capacity");
   HIPX(hipStreamWaitEvent(stream_, plan.ready(), 0));
   const int slot = (instrument_ && pending_ < MAX_PENDING && plan.entries() > 0) ? pending_++ : -1;
-  hipEvent_t e0 = slot >= 0 ? ev_[slot][0] : nullptr, e1 = slot >= 0 ? ev_[slot][1] : nullptr;
+  hipEvent_t e0 = slot >= 0 ? ev_[slot][0].get() : nullptr, e1 = slot >= 0 ? ev_[slot][1].get() : nullptr;
   if (curve_ == Curve::G1)
     run_accumulate<Fq>(plan, bases, part_a_, stream_, e0, e1);
   else
@@ -482,10 +447,11 @@ void MsmEngine::accumulate(const MsmPlan& plan, const MsmBases& bases) {
 
 void MsmEngine::finish(const MsmPlan& plan, uint32_t* d_out, hipStream_t st) {
   if (!st) st = stream_;
+  uint32_t* const sub[2] = {sub_[0], sub_[1]};
   if (curve_ == Curve::G1)
-    run_finish<Fq>(plan, part_a_, part_b_, buckets_, seg_s_, seg_t_, sub_, d_out, st);
+    run_finish<Fq>(plan, part_a_, part_b_, buckets_, seg_s_, seg_t_, sub, d_out, st);
   else
-    run_finish<Fq2>(plan, part_a_, part_b_, buckets_, seg_s_, seg_t_, sub_, d_out, st);
+    run_finish<Fq2>(plan, part_a_, part_b_, buckets_, seg_s_, seg_t_, sub, d_out, st);
 }
 
 void MsmEngine::run(const MsmPlan& plan, const MsmBases& bases, uint32_t* d_out) {

@@ -41,6 +41,8 @@
 #include <string>
 #include <vector>
 
+#include "hip_raii.hpp"
+
 namespace zkp {
 
 struct MsmParams {
@@ -106,9 +108,6 @@ inline int curve_fwords(Curve c) { return c == Curve::G1 ? 8 : 16; }
 class MsmBases {
  public:
   MsmBases(Curve curve, size_t n, int c, int depth);
-  ~MsmBases();
-  MsmBases(const MsmBases&) = delete;
-  MsmBases& operator=(const MsmBases&) = delete;
   // row 0 (n points): the caller fills it (device layout), then extend() derives rows 1..T-1
   uint32_t* row0() { return d_; }
   void extend(hipStream_t st);
@@ -127,19 +126,12 @@ class MsmBases {
   size_t n_;
   int c_, depth_;
   size_t bytes_ = 0;
-  uint32_t* d_ = nullptr;
+  DevBuf<> d_;
 };
 
 class MsmPlan {
-  struct Init {};  // the delegated-to constructor: members only, so a failing allocation in the
-                   // delegating one runs the destructor (no device memory leaks on out-of-memory)
-  MsmPlan(Init, size_t max_n, const MsmParams& prm, hipStream_t stream);
-
  public:
   MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream);
-  ~MsmPlan();
-  MsmPlan(const MsmPlan&) = delete;
-  MsmPlan& operator=(const MsmPlan&) = delete;
   // scalars: device, 8 LE 32-bit words each (standard form, any value < 2^256: reduced below r
   // when loaded, msm_kernels.hpp load_scalar, so W = ceil(255 / c) windows always hold the carry).
   // Enqueues on the plan's stream, never blocks the host (the exact entry count stays on the
@@ -167,7 +159,7 @@ class MsmPlan {
   const uint32_t* bend() const { return bend_; }
   const uint32_t* task_off() const { return off_task_; }
   const uint32_t* perm() const { return perm_; }  // task order (by length)
-  const uint32_t* level_off(int lv) const { return off_lvl_[lv]; }
+  const uint32_t* level_off(int lv) const { return lvl_all_ + (size_t)lv * (nbuckets_ + 1); }
   size_t max_tasks_now() const { return max_tasks_now_; }
   size_t max_tasks() const { return max_tasks_; }
 
@@ -175,38 +167,31 @@ class MsmPlan {
   MsmParams prm_;
   size_t max_n_, n_ = 0;
   hipStream_t stream_;
-  hipEvent_t ready_ = nullptr;
+  Event ready_;
   size_t nbuckets_ = 0, max_entries_ = 0, max_tasks_ = 0, max_tasks_now_ = 0;
   int merge_levels_ = 0;
   uint32_t total_ = 0;
-  uint32_t *vals_sorted_ = nullptr;              // base|sign words in bucket order (the accumulation's input)
-  uint32_t *bstart_ = nullptr, *bend_ = nullptr, *cnt_ = nullptr, *off_task_ = nullptr;
-  std::vector<uint32_t*> off_lvl_;                // merge level l's offsets: lvl_all_ + l * (buckets + 1)
-  uint32_t *lvl_all_ = nullptr, *lvl_tsum_ = nullptr;
+  DevBuf<> vals_sorted_;  // base|sign words in bucket order (the accumulation's input)
+  DevBuf<> bstart_, bend_, cnt_, off_task_;
+  DevBuf<> lvl_all_, lvl_tsum_;  // merge level l's offsets: lvl_all_ + l * (buckets + 1)
   bool dense_ = false;
   // the three-pass LDS-staged bucket sort (hsort_kernels.hpp)
   bool hs_built_ = false;
   uint32_t hs_max_tiles3_ = 0;
-  uint32_t *hs_toff3_ = nullptr, *hs_hist3_ = nullptr, *hs_off3_ = nullptr;
+  DevBuf<> hs_toff3_, hs_hist3_, hs_off3_;
   int hs_b2_ = 0, hs_b3_ = 0, hs_k_ = 1;  // hs_k_: scalars per thread in pass A
   uint32_t hs_nbins_ = 0, hs_nblk_ = 0, hs_max_tiles_ = 0;
-  uint32_t *hs_hist_ = nullptr, *hs_blkoff_ = nullptr, *hs_binbase_ = nullptr;
-  uint32_t *hs_toff_ = nullptr, *hs_hist2_ = nullptr, *hs_off2_ = nullptr, *hs_subbase_ = nullptr;
-  void *hs_ent_a_ = nullptr, *hs_ent_b_ = nullptr;  // 8-byte (key, base|sign) entries
+  DevBuf<> hs_hist_, hs_blkoff_, hs_binbase_;
+  DevBuf<> hs_toff_, hs_hist2_, hs_off2_, hs_subbase_;
+  DevBuf<uint2> hs_ent_a_, hs_ent_b_;  // (key, base|sign) entries
   // accumulate-task order by length (longest first)
-  uint32_t *perm_ = nullptr, *tl_hist_ = nullptr, *tl_off_ = nullptr;
-  uint32_t* tsum_ = nullptr;                    // tile sums of the look-back-free scans
+  DevBuf<> perm_, tl_hist_, tl_off_;
+  DevBuf<> tsum_;  // tile sums of the look-back-free scans
 };
 
 class MsmEngine {
-  struct Init {};  // as MsmPlan::Init
-  MsmEngine(Init, Curve curve, const MsmParams& prm, size_t max_n, hipStream_t stream);
-
  public:
   MsmEngine(Curve curve, const MsmParams& prm, size_t max_n, hipStream_t stream);
-  ~MsmEngine();
-  MsmEngine(const MsmEngine&) = delete;
-  MsmEngine& operator=(const MsmEngine&) = delete;
 
   // sum_i s_i * P_i for the plan's scalars over the bases (bases.n() == plan.n(),
   // same c and depth).  Waits for plan.ready() on the engine's stream, enqueues
@@ -250,13 +235,13 @@ class MsmEngine {
   hipStream_t stream_;
   size_t nbuckets_ = 0, max_tasks_ = 0;
   int fwords_;
-  uint32_t *part_a_ = nullptr, *part_b_ = nullptr, *buckets_ = nullptr;
-  uint32_t *seg_s_ = nullptr, *seg_t_ = nullptr, *sub_[2] = {nullptr, nullptr};
+  DevBuf<> part_a_, part_b_, buckets_;
+  DevBuf<> seg_s_, seg_t_, sub_[2];
   static constexpr int MAX_PENDING = 16;
   bool instrument_ = false;
   int pending_ = 0;
-  hipEvent_t ev_[MAX_PENDING][2] = {};
-  uint32_t* h_counts_ = nullptr;  // pinned: tasks per pending run, then entries per pending run
+  Event ev_[MAX_PENDING][2];
+  PinnedBuf<uint32_t> h_counts_;  // pinned: tasks per pending run, then entries per pending run
   uint32_t h_total_[MAX_PENDING] = {};
   bool h_total_dev_[MAX_PENDING] = {};
   uint32_t h_blocks_[MAX_PENDING] = {};  // entries copied from the device (h_counts_[MAX_PENDING + i])

@@ -550,7 +550,7 @@ HFr fr_pow(const HFr& b, uint64_t e) {
   return r;
 }
 
-uint32_t* upload_powers(const HFr& base, size_t count, uint64_t step_pow, const HFr& mulk, hipStream_t st) {
+DevBuf<> upload_powers(const HFr& base, size_t count, uint64_t step_pow, const HFr& mulk, hipStream_t st) {
   // entries: mulk * base^(i*step_pow)
   std::vector<uint32_t> h(count * 8);
   HFr step = fr_pow(base, step_pow);
@@ -559,8 +559,7 @@ uint32_t* upload_powers(const HFr& base, size_t count, uint64_t step_pow, const 
     fr_to_dev_words(cur, h.data() + i * 8);
     cur = cur * step;
   }
-  uint32_t* d = nullptr;
-  HIPX(hipMalloc(&d, h.size() * 4));
+  DevBuf<> d(h.size());
   HIPX(hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
   HIPX(hipStreamSynchronize(st));
   return d;
@@ -625,19 +624,19 @@ NttEngine::NttEngine(int log_n, hipStream_t stream) : log_n_(log_n), stream_(str
   for (int dir = 0; dir < 2; ++dir)
     for (int b : bits_)
       if (!rtab_[dir][b]) {
-        HIPX(hipMalloc(&rtab_[dir][b], (size_t)RW * MAX_TW * 4));
+        rtab_[dir][b] = DevBuf<>((size_t)RW * MAX_TW);
         hipLaunchKernelGGL(k_root_table, dim3((MAX_TW + TPB - 1) / TPB), dim3(TPB), 0, stream_, rtab_[dir][b],
                            loc_[dir], b);
       }
   // per-pass twiddle tables (one multiply per element instead of lo*hi per element) and
   // the coset key by digit-reversed position: ~3 n x 32 B of HBM
   for (int dir = 0; dir < 2; ++dir) {
-    tw_pass_[dir].assign(bits_.size(), nullptr);
+    tw_pass_[dir].resize(bits_.size());
     for (size_t p = 0; p < bits_.size(); ++p) {
       const int lm = lms_[p], b = bits_[p];
       if (lm == b) continue;  // innermost pass: n2 = 1, no twiddle
       const size_t cnt = size_t(1) << lm;
-      HIPX(hipMalloc(&tw_pass_[dir][p], cnt * 32));
+      tw_pass_[dir][p] = DevBuf<>(cnt * 8);
       table_bytes_ += cnt * 32;
       hipLaunchKernelGGL(k_pass_table, dim3((unsigned)((cnt + TPB - 1) / TPB)), dim3(TPB), 0, stream_,
                          tw_pass_[dir][p], k, lm, b, tw_lo_[dir], tw_hi_[dir], h_);
@@ -645,25 +644,13 @@ NttEngine::NttEngine(int log_n, hipStream_t stream) : log_n_(log_n), stream_(str
   }
   if (k > 0) {
     const size_t n = size_t(1) << k;
-    HIPX(hipMalloc(&coset_pos_, n * 32));
+    coset_pos_ = DevBuf<>(n * 8);
     table_bytes_ += n * 32;
     hipLaunchKernelGGL(k_coset_table, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, stream_, coset_pos_, k,
                        make_pb(bits_), coset_lo_, coset_hi_, h_);
   }
   HIPX(hipGetLastError());
   HIPX(hipStreamSynchronize(stream_));
-}
-
-NttEngine::~NttEngine() {
-  for (uint32_t* p : {tw_lo_[0], tw_lo_[1], tw_hi_[0], tw_hi_[1], loc_[0], loc_[1], coset_lo_, coset_hi_, ninv_,
-                      scratch_, coset_pos_})
-    if (p) (void)hipFree(p);
-  for (auto& v : tw_pass_)
-    for (uint32_t* p : v)
-      if (p) (void)hipFree(p);
-  for (auto& d : rtab_)
-    for (uint32_t* p : d)
-      if (p) (void)hipFree(p);
 }
 
 // mode 0: DIF pass p, 1: DIT (transposed) pass p, 2: fused innermost pass (inverse then forward);
@@ -707,7 +694,7 @@ void NttEngine::scale(uint32_t* data, int mode) {
 
 void NttEngine::digit_reverse(uint32_t* data, bool to_natural) {
   const size_t n = size_t(1) << log_n_;
-  if (!scratch_) HIPX(hipMalloc(&scratch_, n * 32));
+  if (!scratch_) scratch_ = DevBuf<>(n * 8);
   HIPX(hipMemcpyAsync(scratch_, data, n * 32, hipMemcpyDeviceToDevice, stream_));
   hipLaunchKernelGGL(k_digit_reverse, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, stream_, scratch_, data,
                      log_n_, make_pb(bits_), to_natural ? 1 : 0);

@@ -23,14 +23,13 @@
 #include <cstdint>
 #include <vector>
 
+#include "hip_raii.hpp"
+
 namespace zkp {
 
 class NttEngine {
  public:
   NttEngine(int log_n, hipStream_t stream);
-  ~NttEngine();
-  NttEngine(const NttEngine&) = delete;
-  NttEngine& operator=(const NttEngine&) = delete;
 
   int log_n() const { return log_n_; }
   // data: n Fr elements, device layout (Montgomery R' = 2^261, 8 LE words each)
@@ -59,16 +58,15 @@ class NttEngine {
   std::vector<int> lms_;   // block size log of each DIF pass
   int h_ = 0;              // split of the twiddle exponent tables
   // device tables (dev layout): [0] forward root, [1] inverse root
-  uint32_t* tw_lo_[2] = {nullptr, nullptr};
-  uint32_t* tw_hi_[2] = {nullptr, nullptr};
-  std::vector<uint32_t*> tw_pass_[2];      // per DIF pass p: w_(2^lm)^(col*row) by position in block (null: none)
-  uint32_t* loc_[2] = {nullptr, nullptr};  // local roots w_1024^e, e < 512
-  uint32_t* rtab_[2][9] = {};              // [dir][b]: staged stage roots of a b-bit pass (Shoup form)
-  uint32_t* coset_lo_ = nullptr;           // g^e / n, e < 2^h
-  uint32_t* coset_hi_ = nullptr;           // g^(e 2^h)
-  uint32_t* coset_pos_ = nullptr;          // g^f(pos) / n by digit-reversed position
-  uint32_t* ninv_ = nullptr;               // 1/n (dev form)
-  uint32_t* scratch_ = nullptr;            // for digit_reverse (tests only)
+  DevBuf<> tw_lo_[2], tw_hi_[2];
+  std::vector<DevBuf<>> tw_pass_[2];  // per DIF pass p: w_(2^lm)^(col*row) by position in block (empty: none)
+  DevBuf<> loc_[2];                   // local roots w_1024^e, e < 512
+  DevBuf<> rtab_[2][9];               // [dir][b]: staged stage roots of a b-bit pass (Shoup form)
+  DevBuf<> coset_lo_;                 // g^e / n, e < 2^h
+  DevBuf<> coset_hi_;                 // g^(e 2^h)
+  DevBuf<> coset_pos_;                // g^f(pos) / n by digit-reversed position
+  DevBuf<> ninv_;                     // 1/n (dev form)
+  DevBuf<> scratch_;                  // for digit_reverse (tests only)
   size_t table_bytes_ = 0;
 };
 

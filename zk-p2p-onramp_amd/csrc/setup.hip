@@ -15,6 +15,7 @@
 
 #include "curve.hpp"
 #include "hip_check.hpp"
+#include "hip_raii.hpp"
 #include "host_ec.hpp"
 #include "prover.hpp"
 #include "qap.hpp"
@@ -96,32 +97,22 @@ void scale_section(int device, bool g2, const uint8_t* src, uint8_t* dst, size_t
   HIPX(hipSetDevice(device));
   const size_t pb = g2 ? 128 : 64;
   const size_t CH = size_t(1) << 22;  // points per launch: bounded launches, bounded buffer
-  uint32_t* d = nullptr;
-  HIPX(hipMalloc(&d, std::min(count, CH) * pb));
-  hipStream_t st;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  DevBuf<> d(std::min(count, CH) * pb / 4);
+  Stream st(hipStreamNonBlocking);
   const Scalar8 ks = to_scalar8(k);
   const Scalar8 tz = to_scalar8(host::Fq::one().v);  // Montgomery one = 2^256 mod p
-  try {
-    for (size_t at = 0; at < count; at += CH) {
-      const size_t m = std::min(CH, count - at);
-      HIPX(hipMemcpyAsync(d, src + at * pb, m * pb, hipMemcpyHostToDevice, st));
-      const unsigned grid = (unsigned)((m + TPB - 1) / TPB);
-      if (g2)
-        hipLaunchKernelGGL(k_scale_points<Fq2>, dim3(grid), dim3(TPB), 0, st, d, m, ks, tz);
-      else
-        hipLaunchKernelGGL(k_scale_points<Fq>, dim3(grid), dim3(TPB), 0, st, d, m, ks, tz);
-      HIPX(hipGetLastError());
-      HIPX(hipMemcpyAsync(dst + at * pb, d, m * pb, hipMemcpyDeviceToHost, st));
-      HIPX(hipStreamSynchronize(st));
-    }
-  } catch (...) {
-    (void)hipFree(d);
-    (void)hipStreamDestroy(st);
-    throw;
+  for (size_t at = 0; at < count; at += CH) {
+    const size_t m = std::min(CH, count - at);
+    HIPX(hipMemcpyAsync(d, src + at * pb, m * pb, hipMemcpyHostToDevice, st));
+    const unsigned grid = (unsigned)((m + TPB - 1) / TPB);
+    if (g2)
+      hipLaunchKernelGGL(k_scale_points<Fq2>, dim3(grid), dim3(TPB), 0, st, d, m, ks, tz);
+    else
+      hipLaunchKernelGGL(k_scale_points<Fq>, dim3(grid), dim3(TPB), 0, st, d, m, ks, tz);
+    HIPX(hipGetLastError());
+    HIPX(hipMemcpyAsync(dst + at * pb, d, m * pb, hipMemcpyDeviceToHost, st));
+    HIPX(hipStreamSynchronize(st));
   }
-  HIPX(hipFree(d));
-  HIPX(hipStreamDestroy(st));
 }
 
 }  // namespace

@@ -20,6 +20,7 @@
 #include "../../../include/zkp_synth.h"
 #include "../curve.hpp"
 #include "../hip_check.hpp"
+#include "../hip_raii.hpp"
 #include "../host_ec.hpp"
 
 using namespace zkp;
@@ -274,8 +275,7 @@ void fixed_base(int device, const U256* scalars, size_t n, uint8_t* out, const h
   constexpr int FW = sizeof(HF) == sizeof(HFq) ? 8 : 16;
   if (n == 0) return;
   HIPX(hipSetDevice(device));
-  hipStream_t st;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  Stream st(hipStreamNonBlocking);
   std::vector<uint32_t> tbl = make_table(gen);
   uint32_t k256w[8];
   {  // 2^256 mod p as a plain integer in device words
@@ -286,11 +286,7 @@ void fixed_base(int device, const U256* scalars, size_t n, uint8_t* out, const h
     }
   }
   const size_t CH = size_t(1) << 22;
-  uint32_t *dt = nullptr, *dk = nullptr, *ds = nullptr, *dout = nullptr;
-  HIPX(hipMalloc(&dt, tbl.size() * 4));
-  HIPX(hipMalloc(&dk, 32));
-  HIPX(hipMalloc(&ds, std::min(n, CH) * 32));
-  HIPX(hipMalloc(&dout, std::min(n, CH) * 2 * FW * 4));
+  DevBuf<> dt(tbl.size()), dk(8), ds(std::min(n, CH) * 8), dout(std::min(n, CH) * 2 * FW);
   HIPX(hipMemcpyAsync(dt, tbl.data(), tbl.size() * 4, hipMemcpyHostToDevice, st));
   HIPX(hipMemcpyAsync(dk, k256w, 32, hipMemcpyHostToDevice, st));
   for (size_t off = 0; off < n; off += CH) {
@@ -301,8 +297,6 @@ void fixed_base(int device, const U256* scalars, size_t n, uint8_t* out, const h
     HIPX(hipMemcpyAsync(out + off * 2 * FW * 4, dout, m * 2 * FW * 4, hipMemcpyDeviceToHost, st));
     HIPX(hipStreamSynchronize(st));
   }
-  for (void* p : {(void*)dt, (void*)dk, (void*)ds, (void*)dout}) (void)hipFree(p);
-  HIPX(hipStreamDestroy(st));
 }
 
 // ------------------------------------------------------------------ host helpers

@@ -24,6 +24,7 @@
 
 #include "curve.hpp"
 #include "hip_check.hpp"
+#include "hip_raii.hpp"
 #include "host_ec.hpp"
 #include "mpc.hpp"
 #include "prover.hpp"
@@ -152,48 +153,34 @@ static std::vector<uint8_t> lincomb(int device, hipStream_t st, const uint32_t* 
   const uint32_t ntasks = (uint32_t)tlo.size();
   tlo.push_back((uint32_t)terms.size());
   HIPX(hipSetDevice(device));
-  uint32_t *d_idx = nullptr, *d_scal = nullptr, *d_tlo = nullptr, *d_rowtask = nullptr, *d_part = nullptr,
-           *d_out = nullptr;
-  auto release = [&] {
-    for (void* p : {(void*)d_idx, (void*)d_scal, (void*)d_tlo, (void*)d_rowtask, (void*)d_part, (void*)d_out})
-      if (p) (void)hipFree(p);
-  };
-  try {
-    HIPX(hipMalloc(&d_idx, std::max<size_t>(tidx.size(), 1) * 4));
-    HIPX(hipMalloc(&d_scal, std::max<size_t>(tscal.size(), 1) * 4));
-    HIPX(hipMalloc(&d_tlo, tlo.size() * 4));
-    HIPX(hipMalloc(&d_rowtask, rowtask.size() * 4));
-    HIPX(hipMalloc(&d_part, std::max<size_t>(ntasks, 1) * 4 * FWords<F>::W * 4));
-    HIPX(hipMalloc(&d_out, out.size()));
-    if (!tidx.empty()) {
-      HIPX(hipMemcpyAsync(d_idx, tidx.data(), tidx.size() * 4, hipMemcpyHostToDevice, st));
-      HIPX(hipMemcpyAsync(d_scal, tscal.data(), tscal.size() * 4, hipMemcpyHostToDevice, st));
-    }
-    HIPX(hipMemcpyAsync(d_tlo, tlo.data(), tlo.size() * 4, hipMemcpyHostToDevice, st));
-    HIPX(hipMemcpyAsync(d_rowtask, rowtask.data(), rowtask.size() * 4, hipMemcpyHostToDevice, st));
-    if (ntasks)
-      hipLaunchKernelGGL(k_lin_tasks<F>, dim3((ntasks + TPB - 1) / TPB), dim3(TPB), 0, st, d_bases, d_idx, d_scal,
-                         d_tlo, ntasks, d_part);
-    Words8 tz;
-    const host::U256 one = host::Fq::one().v;  // Montgomery one = 2^256 mod p
-    for (int i = 0; i < 4; ++i) tz.w[2 * i] = (uint32_t)one.w[i], tz.w[2 * i + 1] = (uint32_t)(one.w[i] >> 32);
-    hipLaunchKernelGGL(k_lin_rows<F>, dim3((nrows + TPB - 1) / TPB), dim3(TPB), 0, st, d_part, d_rowtask, nrows, tz,
-                       d_out);
-    HIPX(hipGetLastError());
-    HIPX(hipMemcpyAsync(out.data(), d_out, out.size(), hipMemcpyDeviceToHost, st));
-    HIPX(hipStreamSynchronize(st));
-  } catch (...) {
-    release();
-    throw;
+  DevBuf<> d_idx(std::max<size_t>(tidx.size(), 1));
+  DevBuf<> d_scal(std::max<size_t>(tscal.size(), 1));
+  DevBuf<> d_tlo(tlo.size());
+  DevBuf<> d_rowtask(rowtask.size());
+  DevBuf<> d_part(std::max<size_t>(ntasks, 1) * 4 * FWords<F>::W);
+  DevBuf<> d_out(out.size() / 4);
+  if (!tidx.empty()) {
+    HIPX(hipMemcpyAsync(d_idx, tidx.data(), tidx.size() * 4, hipMemcpyHostToDevice, st));
+    HIPX(hipMemcpyAsync(d_scal, tscal.data(), tscal.size() * 4, hipMemcpyHostToDevice, st));
   }
-  release();
+  HIPX(hipMemcpyAsync(d_tlo, tlo.data(), tlo.size() * 4, hipMemcpyHostToDevice, st));
+  HIPX(hipMemcpyAsync(d_rowtask, rowtask.data(), rowtask.size() * 4, hipMemcpyHostToDevice, st));
+  if (ntasks)
+    hipLaunchKernelGGL(k_lin_tasks<F>, dim3((ntasks + TPB - 1) / TPB), dim3(TPB), 0, st, d_bases, d_idx, d_scal, d_tlo,
+                       ntasks, d_part);
+  Words8 tz;
+  const host::U256 one = host::Fq::one().v;  // Montgomery one = 2^256 mod p
+  for (int i = 0; i < 4; ++i) tz.w[2 * i] = (uint32_t)one.w[i], tz.w[2 * i + 1] = (uint32_t)(one.w[i] >> 32);
+  hipLaunchKernelGGL(k_lin_rows<F>, dim3((nrows + TPB - 1) / TPB), dim3(TPB), 0, st, d_part, d_rowtask, nrows, tz, d_out);
+  HIPX(hipGetLastError());
+  HIPX(hipMemcpyAsync(out.data(), d_out, out.size(), hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
   return out;
 }
 
 // a zkey-encoded point array (affine, Montgomery 2^256) uploaded in the device layout
-static uint32_t* upload_points(const uint8_t* src, size_t count, size_t pw, hipStream_t st) {
-  uint32_t* d = nullptr;
-  HIPX(hipMalloc(&d, std::max<size_t>(count * pw, 4)));
+static DevBuf<> upload_points(const uint8_t* src, size_t count, size_t pw, hipStream_t st) {
+  DevBuf<> d(std::max<size_t>(count * pw / 4, 1));
   if (count) {
     HIPX(hipMemcpyAsync(d, src, count * pw, hipMemcpyHostToDevice, st));
     launch_convert_fq_zkey(d, count * pw / 32, st);
@@ -287,31 +274,21 @@ std::vector<uint8_t> zkey_new(int device, const uint8_t* r1cs, size_t r1cs_len, 
   }
   // ---- the GPU sections
   HIPX(hipSetDevice(device));
-  hipStream_t st;
-  HIPX(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  uint32_t *g1b = nullptr, *g2b = nullptr;
   std::vector<uint8_t> sa, sb1, sb2, sl;
-  try {
+  {
+    Stream st(hipStreamNonBlocking);
     // G1 bases: [lTauG1 | lAlphaTauG1 | lBetaTauG1] of level k; G2: lTauG2 of level k
     std::vector<uint8_t> cat((size_t)3 * n * 64);
     std::memcpy(cat.data(), pb.sec[12].ptr + lvl_k * 64, (size_t)n * 64);
     std::memcpy(cat.data() + (size_t)n * 64, pb.sec[14].ptr + lvl_k * 64, (size_t)n * 64);
     std::memcpy(cat.data() + (size_t)2 * n * 64, pb.sec[15].ptr + lvl_k * 64, (size_t)n * 64);
-    g1b = upload_points(cat.data(), (size_t)3 * n, 64, st);
-    g2b = upload_points(pb.sec[13].ptr + lvl_k * 128, n, 128, st);
+    const DevBuf<> g1b = upload_points(cat.data(), (size_t)3 * n, 64, st);
+    const DevBuf<> g2b = upload_points(pb.sec[13].ptr + lvl_k * 128, n, 128, st);
     sa = lincomb<Fq>(device, st, g1b, std::move(ta), n_vars);
     sb1 = lincomb<Fq>(device, st, g1b, tb, n_vars);
     sb2 = lincomb<Fq2>(device, st, g2b, std::move(tb), n_vars);
     sl = lincomb<Fq>(device, st, g1b, std::move(tl), n_vars);
-  } catch (...) {
-    if (g1b) (void)hipFree(g1b);
-    if (g2b) (void)hipFree(g2b);
-    (void)hipStreamDestroy(st);
-    throw;
   }
-  HIPX(hipFree(g1b));
-  HIPX(hipFree(g2b));
-  HIPX(hipStreamDestroy(st));
   // ---- assemble the zkey (sections 1..10 in order)
   auto lem_fq = [](const host::U256& v, std::vector<uint8_t>& o) { put_u256(o, host::Fq::from_std(v).v); };
   auto u256 = [](const char* dec) {  // decimal -> U256 (generator constants)
