@@ -1,6 +1,6 @@
 """The device field and curve code (csrc/field.hpp, curve.hpp: __host__ __device__)
 compiled for the host by hipcc and checked op by op against the oracle -- the lazy
-reductions (lsub/rsub/sub_2x/mul2/mul4, Fq2 products) at their extreme operand
+reductions (lsub/rsub/sub_2x/mul2, Fq2 products) at their extreme operand
 ranges, and XYZZ additions/doublings.  CPU-only: exercises the exact arithmetic the
 kernels run, without a GPU."""
 import os

@@ -113,7 +113,7 @@ def main(n=300):
         wq = (wv << 261) // R
         lines.append("shoupr %s %s %s" % (l9(a, raw=k % 2 == 1), w8(wv), l9(wq)))
         checks.append(("shoupr", lambda z, a=a, wv=wv: z % R == a * wv % R and z < 3 * R))
-    # round-5 NTT unit (ntt.hip r4_unit, field.hpp sub_raw6n): tile values < 3r normalised, at the value
+    # round-5 NTT unit (ntt.hip r4_unit, field.hpp sub_raw8): tile values < 3r normalised, at the value
     # extreme (3r - 1) and at the limb extreme (every low limb 2^29 - 1, top limb just below 3r's);
     # tw a table value < 2r (Montgomery), w a plain root < r with its Shoup quotient
     lowmax = (1 << 232) - 1
@@ -199,11 +199,61 @@ def main(n=300):
         c1 = t0 * r1 + t1 * r0 + d0 * y1 + d1 * y0
         for x in (c0, c1):
             checks.append(("y3f2", lambda v, x=x: v % P == x * inv_rp_p % P and v < 2 * P))
+    # lockstep pairs (field.hpp mul_pair / sqr_pair / mul_shoup_pair: the two-lane instances of the
+    # product cores): the two lanes get DIFFERENT operands, each lane is checked against the oracle
+    # and must equal the 1-lane form bit for bit, and the same pair with its lanes swapped must give
+    # the swapped results.  A lane is (operand limbs, the value its result is congruent to).
+    same = []  # (output line i, output line j, name): must be identical
+
+    def pairs(op, name, m, lanes, bound):
+        for k, x in enumerate(lanes):
+            y = lanes[(k + len(lanes) // 2 + 1) % len(lanes)]
+            b0 = len(checks)
+            for u, v in ((x, y), (y, x)):
+                b = len(checks)
+                lines.append("%s %s %s" % (op, u[0], v[0]))
+                for t in (u, v, u, v):  # the pair's lanes, then the 1-lane products
+                    checks.append((name, lambda z, w=t[1], m=m: z % m == w % m and z < bound))
+                same.extend([(b, b + 2, name + "_vs_1lane"), (b + 1, b + 3, name + "_vs_1lane")])
+            same.extend([(b0, b0 + 5, name + "_swap"), (b0 + 1, b0 + 4, name + "_swap")])
+
+    for f, m, inv in (("q", P, inv_rp_p), ("r", R, inv_rp_r)):
+        # mul: the value extremes up to the largest allowed operand 8m - 1, and ONE raw operand (an rsub
+        # result: value < 6m, limbs up to just below 2^31) against a normalised one, on either side
+        big = [0, 1, m - 1, m, 2 * m - 1, 8 * m - 1]
+        ml = [("%s %s" % (l9(a), l9(b)), a * b * inv) for a in big for b in big]
+        for a in (6 * m - 1, 4 * m + 1):
+            for b in (2 * m - 1, 8 * m - 1, 1):
+                ml.append(("%s %s" % (l9(a, raw=True), l9(b)), a * b * inv))
+                ml.append(("%s %s" % (l9(b), l9(a, raw=True)), a * b * inv))
+        for _ in range(n):
+            a, b = rnd.randrange(8 * m), rnd.randrange(8 * m)
+            ml.append(("%s %s" % (l9(a), l9(b)), a * b * inv))
+        pairs("mulp" + f, "mul_pair_" + f, m, ml, 2 * m)
+        # sqr: up to a value of 11m (121 m^2 < 169 m^2)
+        sl = [(l9(a), a * a * inv) for a in big + [11 * m] + [rnd.randrange(11 * m) for _ in range(n)]]
+        pairs("sqrp" + f, "sqr_pair_" + f, m, sl, 2 * m)
+    # Shoup pairs (Fr only, as the NTT uses them): a up to 2^261 - 1, raw limbs just below 2^31, and the
+    # sub_raw8 extreme, every low limb at 2.5 * 2^30 - 1 with a top limb that keeps the value near 14r
+    lim25 = [(5 << 29) - 1] * 8 + [(14 * R >> 232) - 5]
+    a25 = sum(v << (29 * i) for i, v in enumerate(lim25))
+    assert 13 * R < a25 < 14 * R
+    al = [(l9(a), a) for a in (0, 1, R - 1, R, 2 * R - 1, (1 << 261) - 1)]
+    al += [(l9(a, raw=True), a) for a in ((1 << 261) - 1, 14 * R - 1)] + [(" ".join("%x" % v for v in lim25), a25)]
+    al += [(l9(a, raw=k % 2 == 1), a) for k, a in enumerate(rnd.randrange(1 << 261) for _ in range(n))]
+    shl = []
+    for k, (astr, a) in enumerate(al):
+        for wv in (R - 1, 1, 0, rnd.randrange(R)) if k < 9 else (rnd.randrange(R),):
+            shl.append(("%s %s %s" % (astr, w8(wv), l9((wv << 261) // R)), a * wv))
+    pairs("shouppr", "mul_shoup_pair_r", R, shl, 3 * R)
     for z in (0, P):
         lines.append("iszq %s" % w8(z)); checks.append(("iszq", lambda v: v == 1))
     out = subprocess.run([BIN], input="\n".join(lines) + "\n", capture_output=True, text=True).stdout.strip().split("\n")
     assert len(out) == len(checks), (len(out), len(checks))
     bad = {}
+    for i, j, name in same:
+        if out[i].split() != out[j].split():
+            bad[name] = bad.get(name, 0) + 1
     for (name, fn), o in zip(checks, out):
         if name == "iszq":
             v = int(o)

@@ -14,6 +14,25 @@ template <class C> static void prf(const Fe<C>& x) { uint32_t w[8]; pack(x, w); 
 // 9 hex 29-bit limbs (values up to 2^261, e.g. a Shoup quotient)
 template <class C> static Fe<C> rdl() { Fe<C> x; for (int i = 0; i < NL; ++i) if (scanf("%x", &x.v[i]) != 1) exit(1); return x; }
 
+// The lockstep pairs (the L = 2 instances of field.hpp's product cores), all operands as 9 limbs so
+// that values above 2^256 and unnormalised limbs can be given; lane 0's operands first, then lane 1's.
+// Print both lanes of the pair, then the same two products by the 1-lane form.
+template <class C> static void mul_pair_op() {
+  Fe<C> a = rdl<C>(), b = rdl<C>(), c = rdl<C>(), d = rdl<C>(), r, s;
+  mul_pair(a, b, c, d, r, s);
+  prf(r); printf("\n"); prf(s); printf("\n"); prf(mul(a, b)); printf("\n"); prf(mul(c, d));
+}
+template <class C> static void sqr_pair_op() {
+  Fe<C> a = rdl<C>(), c = rdl<C>(), r, s;
+  sqr_pair(a, c, r, s);
+  prf(r); printf("\n"); prf(s); printf("\n"); prf(sqr(a)); printf("\n"); prf(sqr(c));
+}
+template <class C> static void mul_shoup_pair_op() {  // per lane: a (limbs), w (words, plain), wq (limbs)
+  Fe<C> a = rdl<C>(), w = rdf<C>(), wq = rdl<C>(), c = rdl<C>(), v = rdf<C>(), vq = rdl<C>(), r, s;
+  mul_shoup_pair(a, w, wq, c, v, vq, r, s);
+  prf(r); printf("\n"); prf(s); printf("\n"); prf(mul_shoup(a, w, wq)); printf("\n"); prf(mul_shoup(c, v, vq));
+}
+
 int main() {
   char op[32];
   while (scanf("%31s", op) == 1) {
@@ -47,10 +66,10 @@ int main() {
       Fr x0 = rdf<FrCfg>(), x1 = rdf<FrCfg>(), x2 = rdf<FrCfg>(), x3 = rdf<FrCfg>(), w = rdf<FrCfg>();
       Fr wq = rdl<FrCfg>(), tw = rdf<FrCfg>();
       const Fr s02 = add_raw(x0, x2), s13 = add_raw(x1, x3);
-      prf(mul_shoup(sub_raw6n(s02, s13), w, wq)); printf("\n");   // full unit: y1 (< 3m)
-      prf(qreduce(sub_raw6n(s02, s13))); printf("\n");            // stored last pair: p1 (< 1.2m)
+      prf(mul_shoup(sub_raw8(s02, s13), w, wq)); printf("\n");    // full unit: y1 (< 3m)
+      prf(qreduce(sub_raw8(s02, s13))); printf("\n");             // stored last pair: p1 (< 1.2m)
       prf(mul(add_raw(s02, s13), tw)); printf("\n");              // raw last pair p0 x twiddle (< 2m)
-      prf(mul(sub_raw6n(s02, s13), tw)); printf("\n");            // raw p1 x twiddle
+      prf(mul(sub_raw8(s02, s13), tw)); printf("\n");             // raw p1 x twiddle
       prf(mul(add_raw(x0, x2), tw)); printf("\n");                // raw p2 (d02 + d13, each < 3m)
       prf(mul(rsub(x0, x2), tw)); printf("\n");                   // raw p3 / odd stage x - y + 4m
       // last pair (Hh == 1): d02 = x0 - x2 by the root w^0, only reduced; d13 a Shoup product
@@ -98,6 +117,11 @@ int main() {
           y{rdf<FqCfg>(), rdf<FqCfg>()};
       Fq2 v = acc_y3(r, t, y, d); prf(v.c0); printf("\n"); prf(v.c1);
     }
+    else if (o == "mulpq") mul_pair_op<FqCfg>();
+    else if (o == "mulpr") mul_pair_op<FrCfg>();
+    else if (o == "sqrpq") sqr_pair_op<FqCfg>();
+    else if (o == "sqrpr") sqr_pair_op<FrCfg>();
+    else if (o == "shouppr") mul_shoup_pair_op<FrCfg>();
     else if (o == "addr") { Fr a = rdf<FrCfg>(), b = rdf<FrCfg>(); prf(add(a, b)); }
     else if (o == "subr") { Fr a = rdf<FrCfg>(), b = rdf<FrCfg>(); prf(sub(a, b)); }
     else if (o == "qredq") { Fq a = rdf<FqCfg>(); prf(qreduce(a)); }

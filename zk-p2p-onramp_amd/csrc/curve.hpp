@@ -25,16 +25,19 @@ struct Xyzz {
   F x, y, zz, zzz;
 };
 
-// zero / one of a base field (any Fe<C>: Fq, or Fq as the accumulation computes it) or of Fq2
+// zero / one of a base field (any Fe<C>: Fq, or Fq as the accumulation computes it) or of Fq2, and
+// whether two independent products of it run as a lockstep pair (mul_2 / acc_sqr_2 below)
 template <class F>
 struct FConst;
 template <class C>
 struct FConst<Fe<C>> {
+  static constexpr bool LOCKSTEP = C::CHAIN;
   static ZDEV Fe<C> zero() { return fe_zero<C>(); }
   static ZDEV Fe<C> one() { return fe_one<C>(); }
 };
 template <>
 struct FConst<Fq2> {
+  static constexpr bool LOCKSTEP = false;
   static ZDEV Fq2 zero() { return Fq2{fe_zero<FqCfg>(), fe_zero<FqCfg>()}; }
   static ZDEV Fq2 one() { return Fq2{fe_one<FqCfg>(), fe_zero<FqCfg>()}; }
 };
@@ -79,12 +82,7 @@ ZDEV Fq2 acc_xcanon(const Fq2& x) { return canon4(x); }
 // plain products (a lockstep triple measured no better, profiles/mul_pairs_r03.txt)
 template <class F>
 ZDEV void mul_2(const F& a, const F& b, const F& c, const F& d, F& r, F& s) {
-  r = mul(a, b);
-  s = mul(c, d);
-}
-template <class C>
-ZDEV void mul_2(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c, const Fe<C>& d, Fe<C>& r, Fe<C>& s) {
-  if constexpr (C::CHAIN) {
+  if constexpr (FConst<F>::LOCKSTEP) {
     mul_pair(a, b, c, d, r, s);
   } else {
     r = mul(a, b);
@@ -93,12 +91,7 @@ ZDEV void mul_2(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c, const Fe<C>& d, 
 }
 template <class F>
 ZDEV void acc_sqr_2(const F& a, const F& c, F& r, F& s) {
-  r = acc_sqr(a);
-  s = acc_sqr(c);
-}
-template <class C>
-ZDEV void acc_sqr_2(const Fe<C>& a, const Fe<C>& c, Fe<C>& r, Fe<C>& s) {
-  if constexpr (C::CHAIN) {
+  if constexpr (FConst<F>::LOCKSTEP) {
     sqr_pair(a, c, r, s);
   } else {
     r = acc_sqr(a);
@@ -131,14 +124,6 @@ ZDEV bool maybe_zero(const Fq2& a) { return maybe_zero(a.c0) && maybe_zero(a.c1)
 template <class F>
 ZDEV bool aff_is_inf(const Aff<F>& p) { return is_zero_raw(p.x) && is_zero_raw(p.y); }
 
-template <class F>
-ZDEV Aff<F> aff_neg(const Aff<F>& p) {
-  Aff<F> r;
-  r.x = p.x;
-  r.y = sub(f_zero<F>(), p.y);
-  return r;
-}
-
 // 2 * (x, y), affine input (mdbl-2008-s-1)
 template <class F>
 ZDEV Xyzz<F> xyzz_dbl_aff(const Aff<F>& p) {
@@ -159,21 +144,12 @@ ZDEV Xyzz<F> xyzz_dbl_aff(const Aff<F>& p) {
 // 2 * P (dbl-2008-s-1, a = 0); p.x may be a lazily reduced accumulator x (acc_xcanon first:
 // the doubling formulas take canonical coordinates)
 template <class F>
-ZDEV Xyzz<F> xyzz_dbl(const Xyzz<F>& p_in) {
-  if (xyzz_is_inf(p_in)) return p_in;
-  Xyzz<F> p = p_in;
-  p.x = acc_xcanon(p.x);
-  F U = dbl(p.y);
-  F V = sqr(U);
-  F W = mul(U, V);
-  F S = mul(p.x, V);
-  F X2 = sqr(p.x);
-  F M = add(dbl(X2), X2);
-  Xyzz<F> r;
-  r.x = sub_2x(sqr(M), f_zero<F>(), S);
-  r.y = mul2(M, lsub(S, r.x), W, lsub(f_zero<F>(), p.y));  // M (S - X3) - W Y
-  r.zz = mul(V, p.zz);
-  r.zzz = mul(W, p.zzz);
+ZDEV Xyzz<F> xyzz_dbl(const Xyzz<F>& p) {
+  if (xyzz_is_inf(p)) return p;
+  // the affine doubling of (X, Y), whose ZZ3 = V and ZZZ3 = W then take the factors ZZ and ZZZ
+  Xyzz<F> r = xyzz_dbl_aff(Aff<F>{acc_xcanon(p.x), p.y});
+  r.zz = mul(r.zz, p.zz);
+  r.zzz = mul(r.zzz, p.zzz);
   return r;
 }
 
@@ -287,13 +263,6 @@ ZDEV void xyzz_add(Xyzz<F>& acc, const Xyzz<F>& q) {
   mul_2(ZZ, PP, ZZZ, PPP, acc.zz, acc.zzz);
   acc.x = X3;
   acc.y = Y3;
-}
-
-template <class F>
-ZDEV Xyzz<F> xyzz_neg(const Xyzz<F>& p) {
-  Xyzz<F> r = p;
-  r.y = sub(f_zero<F>(), p.y);
-  return r;
 }
 
 // XYZZ -> affine (x = X/ZZ, y = Y/ZZZ) with one inversion of ZZ*ZZZ; infinity -> (0, 0)

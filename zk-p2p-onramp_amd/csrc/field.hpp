@@ -79,112 +79,156 @@ ZDEV Fe<C> fe_const(const uint32_t (&k)[NL]) {
 template <class C>
 ZDEV Fe<C> fe_one() { return fe_const<C>(C::ONE); }
 
-// Montgomery product a*b/2^261 mod m (FIPS / product scanning).
-// Inputs: limbs 0..7 < 2^30, value < 8m.  Output: normalised limbs, value < 2m.
-template <class C>
-ZDEV Fe<C> mul(const Fe<C>& a, const Fe<C>& b) {
-  uint32_t m[NL];
-  Fe<C> r;
-  uint64_t acc = 0;
+// ---------------------------------------------------------------- product cores
+// Every field product is one of three product-scanning column loops, each written once for L
+// independent LANES in lockstep.  With chained columns (CH) the lanes' chains interleave, so a
+// dependent mad of one chain follows an independent mad of the other instead of a wait state; L = 1
+// is the plain form.  The statement order inside a column is what the scheduler sees and is the
+// tuning knob: the products of all lanes for one (j, k), then the constant (m MOD / q NM) terms lane
+// by lane.  All loops unroll fully; the operand arrays of pointers cost nothing.
+#define ZLANES _Pragma("unroll") for (int l = 0; l < L; ++l)
+
+// Montgomery sum of products (FIPS / product scanning): r[l] = sum_k a[l][k] b[l][k] / 2^261 mod m
+// with ONE reduction per lane ("lazy reduction": the N products' and the m MOD partial products of a
+// column accumulate together).  Column i takes a_j b_(i-j) for every j in range; m_i, the quotient
+// digit that clears the column, is fixed once the column's last product (j = i) is in.
+//   N = 1: a's limbs 0..7 < 2^30 (value < 8m; up to ~11m as long as a b < 169 m^2), or ONE operand
+//          with limbs < 2^31 against a normalised one (column sums < 9*2^60 + 9*2^58 + 2^35 < 2^64).
+//   N > 1: all operands normalised (limbs < 2^29; N = 4: columns hold <= 36 + 9 partial products
+//          < 2^58, < 2^63.5) and the sum < m 2^261 (~169 m^2).
+// Output: normalised limbs, value < 2m (sum / 2^261 + m).
+template <class C, bool CH, int L, int N>
+ZDEV void mont_sop(const Fe<C>* const (&a)[L][N], const Fe<C>* const (&b)[L][N], Fe<C>* const (&r)[L]) {
+  uint32_t m[L][NL];
+  uint64_t acc[L];
+  ZLANES acc[l] = 0;
 #pragma unroll
-  for (int i = 0; i < NL; ++i) {
+  for (int i = 0; i < 2 * NL - 1; ++i) {
 #pragma unroll
-    for (int j = 0; j < i; ++j) {
-      mac<C::CHAIN>(acc, a.v[j], b.v[i - j]);
-      mac_k<C::CHAIN>(acc, m[j], C::MOD[i - j]);
+    for (int j = (i < NL ? 0 : i - NL + 1); j <= (i < NL ? i : NL - 1); ++j) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) ZLANES mac<CH>(acc[l], a[l][k]->v[j], b[l][k]->v[i - j]);
+      if (j == i) ZLANES m[l][i] = ((uint32_t)acc[l] * C::INV) & LMASK;
+      ZLANES mac_k<CH>(acc[l], m[l][j], C::MOD[i - j]);
     }
-    mac<C::CHAIN>(acc, a.v[i], b.v[0]);
-    m[i] = ((uint32_t)acc * C::INV) & LMASK;
-    mac_k<C::CHAIN>(acc, m[i], C::MOD[0]);
-    acc >>= LB;
+    if (i >= NL) ZLANES r[l]->v[i - NL] = (uint32_t)acc[l] & LMASK;
+    ZLANES acc[l] >>= LB;
   }
-#pragma unroll
-  for (int i = NL; i < 2 * NL - 1; ++i) {
-#pragma unroll
-    for (int j = i - NL + 1; j < NL; ++j) {
-      mac<C::CHAIN>(acc, a.v[j], b.v[i - j]);
-      mac_k<C::CHAIN>(acc, m[j], C::MOD[i - j]);
-    }
-    r.v[i - NL] = (uint32_t)acc & LMASK;
-    acc >>= LB;
-  }
-  r.v[NL - 1] = (uint32_t)acc;
-  return r;
+  ZLANES r[l]->v[NL - 1] = (uint32_t)acc[l];
 }
 
-// Product by a CONSTANT with a precomputed quotient (Shoup): a w mod m for w < m given as plain
-// limbs and wq = floor(w 2^261 / m) (both normalised, 9 limbs).  q = floor(a wq / 2^261) from the
-// product columns 7..17 only (the dropped columns 0..6 sum to < 2^237, so q is the exact floor or
-// one less), then a w - q m = (a w + q (2^261 - m)) mod 2^261 from the low columns 0..8.  Since
-// a w / m - a wq / 2^261 < a / 2^261 <= 1, the result is in [0, 3m).  a: limbs < 2^31 (a raw sum
-// or borrow-form difference is fine), value < 2^261.  A Montgomery-form a stays in Montgomery
+// Montgomery squares r[l] = a[l]^2 / 2^261 mod m: cross products computed once against a doubled
+// operand.  Operand and output as mont_sop with N = 1 (a < 11m).
+template <class C, bool CH, int L>
+ZDEV void mont_sqr(const Fe<C>* const (&a)[L], Fe<C>* const (&r)[L]) {
+  uint32_t m[L][NL], d[L][NL];
+#pragma unroll
+  for (int i = 0; i < NL; ++i) ZLANES d[l][i] = a[l]->v[i] << 1;
+  uint64_t acc[L];
+  ZLANES acc[l] = 0;
+#pragma unroll
+  for (int i = 0; i < 2 * NL - 1; ++i) {
+    const int lo = i < NL ? 0 : i - NL + 1, hi = i < NL ? i : NL - 1;
+#pragma unroll
+    for (int j = lo; j < (i + 1) / 2; ++j) ZLANES mac<CH>(acc[l], d[l][j], a[l]->v[i - j]);
+    if ((i & 1) == 0) ZLANES mac<CH>(acc[l], a[l]->v[i / 2], a[l]->v[i / 2]);
+#pragma unroll
+    for (int j = lo; j <= hi; ++j) {
+      if (j == i) ZLANES m[l][i] = ((uint32_t)acc[l] * C::INV) & LMASK;
+      ZLANES mac_k<CH>(acc[l], m[l][j], C::MOD[i - j]);
+    }
+    if (i >= NL) ZLANES r[l]->v[i - NL] = (uint32_t)acc[l] & LMASK;
+    ZLANES acc[l] >>= LB;
+  }
+  ZLANES r[l]->v[NL - 1] = (uint32_t)acc[l];
+}
+
+// Products by CONSTANTS with precomputed quotients (Shoup): r[l] = a[l] w[l] mod m for w < m given
+// as plain limbs and wq = floor(w 2^261 / m) (both normalised, 9 limbs).  q = floor(a wq / 2^261)
+// from the product columns 7..17 only (the dropped columns 0..6 sum to < 2^237, so q is the exact
+// floor or one less), then a w - q m = (a w + q (2^261 - m)) mod 2^261 from the low columns 0..8.
+// Since a w / m - a wq / 2^261 < a / 2^261 <= 1, the result is in [0, 3m).  a: limbs < 2^31 (a raw
+// sum or borrow-form difference is fine), value < 2^261.  A Montgomery-form a stays in Montgomery
 // form (w is plain).  143 v_mad_u64_u32 and no per-column quotient digits, against 162 mads plus
 // 9 v_mul_lo_u32 for mul(); NTT roots, twiddles and the coset key are all constants.
-template <class C>
-ZDEV Fe<C> mul_shoup(const Fe<C>& a, const Fe<C>& w, const Fe<C>& wq) {
-  uint32_t q[NL];
-  uint64_t acc = 0;
+template <class C, int L>
+ZDEV void mont_shoup(const Fe<C>* const (&a)[L], const Fe<C>* const (&w)[L], const Fe<C>* const (&wq)[L],
+                     Fe<C>* const (&r)[L]) {
+  uint32_t q[L][NL];
+  uint64_t acc[L];
+  ZLANES acc[l] = 0;
 #pragma unroll
   for (int c = 7; c < 2 * NL - 1; ++c) {
 #pragma unroll
-    for (int i = (c - NL + 1 > 0 ? c - NL + 1 : 0); i <= (c < NL - 1 ? c : NL - 1); ++i) mac<C::CHAIN>(acc, a.v[i], wq.v[c - i]);
-    if (c >= NL) q[c - NL] = (uint32_t)acc & LMASK;
-    acc >>= LB;
+    for (int i = (c < NL ? 0 : c - NL + 1); i <= (c < NL ? c : NL - 1); ++i)
+      ZLANES mac<C::CHAIN>(acc[l], a[l]->v[i], wq[l]->v[c - i]);
+    if (c >= NL) ZLANES q[l][c - NL] = (uint32_t)acc[l] & LMASK;
+    ZLANES acc[l] >>= LB;
   }
-  q[NL - 1] = (uint32_t)acc;  // columns 9..16 give q's limbs 0..7, the carry out its top limb (q < 2^261)
-  Fe<C> r;
-  acc = 0;
+  ZLANES q[l][NL - 1] = (uint32_t)acc[l];  // columns 9..16 give q's limbs 0..7, the carry out its top limb (q < 2^261)
+  ZLANES acc[l] = 0;
 #pragma unroll
   for (int c = 0; c < NL; ++c) {
 #pragma unroll
     for (int i = 0; i <= c; ++i) {
-      mac<C::CHAIN>(acc, a.v[i], w.v[c - i]);
-      mac_k<C::CHAIN>(acc, q[i], C::NM[c - i]);
+      ZLANES mac<C::CHAIN>(acc[l], a[l]->v[i], w[l]->v[c - i]);
+      ZLANES mac_k<C::CHAIN>(acc[l], q[l][i], C::NM[c - i]);
     }
-    r.v[c] = (uint32_t)acc & LMASK;
-    acc >>= LB;
+    ZLANES r[l]->v[c] = (uint32_t)acc[l] & LMASK;
+    ZLANES acc[l] >>= LB;
   }
+}
+#undef ZLANES
+
+// Montgomery product a*b/2^261 mod m.
+// Inputs: limbs 0..7 < 2^30, value < 8m.  Output: normalised limbs, value < 2m.
+template <class C>
+ZDEV Fe<C> mul(const Fe<C>& a, const Fe<C>& b) {
+  Fe<C> r;
+  mont_sop<C, C::CHAIN, 1, 1>({{&a}}, {{&b}}, {&r});
   return r;
 }
 
-// two independent Shoup products a w, c v in lockstep (column chains interleaved, as mul_pair)
+// (a*b + c*d)/2^261 mod m with ONE reduction.  All four operands normalised (limbs < 2^29; column
+// sums <= 27 * 2^58 < 2^63) and a*b + c*d < m*2^261 (~169 m^2) for an output < 2m.  Used for
+// Y3 = R (Q - X3) - Y1 PPP as R*(Q - X3) + Y1*(2m - PPP): one reduction and no
+// subtraction instead of two multiplies and a subtraction (~230 instructions saved).
+template <class C>
+ZDEV Fe<C> mul2(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c, const Fe<C>& d) {
+  Fe<C> r;
+  mont_sop<C, C::CHAIN, 1, 2>({{&a, &c}}, {{&b, &d}}, {&r});
+  return r;
+}
+
+template <class C>
+ZDEV Fe<C> sqr(const Fe<C>& a) {
+  Fe<C> r;
+  mont_sqr<C, C::CHAIN, 1>({&a}, {&r});
+  return r;
+}
+
+// a w for a constant w with its Shoup quotient wq (mont_shoup): output in [0, 3m)
+template <class C>
+ZDEV Fe<C> mul_shoup(const Fe<C>& a, const Fe<C>& w, const Fe<C>& wq) {
+  Fe<C> r;
+  mont_shoup<C, 1>({&a}, {&w}, {&wq}, {&r});
+  return r;
+}
+
+// Two independent products r = a b, s = c d / squares r = a^2, s = c^2 / Shoup products r = a w,
+// s = c v in lockstep.  Same arithmetic as mul() / sqr() / mul_shoup() on each pair.
+template <class C>
+ZDEV void mul_pair(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c, const Fe<C>& d, Fe<C>& r, Fe<C>& s) {
+  mont_sop<C, C::CHAIN, 2, 1>({{&a}, {&c}}, {{&b}, {&d}}, {&r, &s});
+}
+template <class C>
+ZDEV void sqr_pair(const Fe<C>& a, const Fe<C>& c, Fe<C>& r, Fe<C>& s) {
+  mont_sqr<C, C::CHAIN, 2>({&a, &c}, {&r, &s});
+}
 template <class C>
 ZDEV void mul_shoup_pair(const Fe<C>& a, const Fe<C>& w, const Fe<C>& wq, const Fe<C>& c, const Fe<C>& v,
                          const Fe<C>& vq, Fe<C>& r, Fe<C>& s) {
-  uint32_t q[NL], p[NL];
-  uint64_t x = 0, y = 0;
-#pragma unroll
-  for (int k = 7; k < 2 * NL - 1; ++k) {
-#pragma unroll
-    for (int i = (k - NL + 1 > 0 ? k - NL + 1 : 0); i <= (k < NL - 1 ? k : NL - 1); ++i) {
-      mac<C::CHAIN>(x, a.v[i], wq.v[k - i]);
-      mac<C::CHAIN>(y, c.v[i], vq.v[k - i]);
-    }
-    if (k >= NL) {
-      q[k - NL] = (uint32_t)x & LMASK;
-      p[k - NL] = (uint32_t)y & LMASK;
-    }
-    x >>= LB;
-    y >>= LB;
-  }
-  q[NL - 1] = (uint32_t)x;
-  p[NL - 1] = (uint32_t)y;
-  x = 0;
-  y = 0;
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-#pragma unroll
-    for (int i = 0; i <= k; ++i) {
-      mac<C::CHAIN>(x, a.v[i], w.v[k - i]);
-      mac<C::CHAIN>(y, c.v[i], v.v[k - i]);
-      mac_k<C::CHAIN>(x, q[i], C::NM[k - i]);
-      mac_k<C::CHAIN>(y, p[i], C::NM[k - i]);
-    }
-    r.v[k] = (uint32_t)x & LMASK;
-    s.v[k] = (uint32_t)y & LMASK;
-    x >>= LB;
-    y >>= LB;
-  }
+  mont_shoup<C, 2>({&a, &c}, {&w, &v}, {&wq, &vq}, {&r, &s});
 }
 
 // Shoup quotient of a constant from its canonical Montgomery form wm = w 2^261 mod m (< m):
@@ -211,232 +255,12 @@ ZDEV Fe<C> shoup_quot(const Fe<C>& wm) {
   return r;
 }
 
-// Montgomery product of a SUM of two products, (a*b + c*d)/2^261 mod m, with ONE
-// reduction ("lazy reduction"): the a*b, c*d and m*MOD partial products of a column
-// accumulate together.  All four operands normalised (limbs < 2^29; column sums
-// <= 27 * 2^58 < 2^63) and a*b + c*d < m*2^261 (~169 m^2) for an output < 2m.  Used for
-// Y3 = R (Q - X3) - Y1 PPP as R*(Q - X3) + Y1*(2m - PPP): one reduction and no
-// subtraction instead of two multiplies and a subtraction (~230 instructions saved).
-template <class C>
-ZDEV Fe<C> mul2(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c, const Fe<C>& d) {
-  uint32_t m[NL];
-  Fe<C> r;
-  uint64_t acc = 0;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-#pragma unroll
-    for (int j = 0; j < i; ++j) {
-      mac<C::CHAIN>(acc, a.v[j], b.v[i - j]);
-      mac<C::CHAIN>(acc, c.v[j], d.v[i - j]);
-      mac_k<C::CHAIN>(acc, m[j], C::MOD[i - j]);
-    }
-    mac<C::CHAIN>(acc, a.v[i], b.v[0]);
-    mac<C::CHAIN>(acc, c.v[i], d.v[0]);
-    m[i] = ((uint32_t)acc * C::INV) & LMASK;
-    mac_k<C::CHAIN>(acc, m[i], C::MOD[0]);
-    acc >>= LB;
-  }
-#pragma unroll
-  for (int i = NL; i < 2 * NL - 1; ++i) {
-#pragma unroll
-    for (int j = i - NL + 1; j < NL; ++j) {
-      mac<C::CHAIN>(acc, a.v[j], b.v[i - j]);
-      mac<C::CHAIN>(acc, c.v[j], d.v[i - j]);
-      mac_k<C::CHAIN>(acc, m[j], C::MOD[i - j]);
-    }
-    r.v[i - NL] = (uint32_t)acc & LMASK;
-    acc >>= LB;
-  }
-  r.v[NL - 1] = (uint32_t)acc;
-  return r;
-}
-
-// Squaring: cross products computed once against a doubled operand.
-template <class C>
-ZDEV Fe<C> sqr(const Fe<C>& a) {
-  uint32_t m[NL], d[NL];
-#pragma unroll
-  for (int i = 0; i < NL; ++i) d[i] = a.v[i] << 1;
-  Fe<C> r;
-  uint64_t acc = 0;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-#pragma unroll
-    for (int j = 0; j < (i + 1) / 2; ++j) mac<C::CHAIN>(acc, d[j], a.v[i - j]);
-    if ((i & 1) == 0) mac<C::CHAIN>(acc, a.v[i / 2], a.v[i / 2]);
-#pragma unroll
-    for (int j = 0; j < i; ++j) mac_k<C::CHAIN>(acc, m[j], C::MOD[i - j]);
-    m[i] = ((uint32_t)acc * C::INV) & LMASK;
-    mac_k<C::CHAIN>(acc, m[i], C::MOD[0]);
-    acc >>= LB;
-  }
-#pragma unroll
-  for (int i = NL; i < 2 * NL - 1; ++i) {
-#pragma unroll
-    for (int j = i - NL + 1; j < (i + 1) / 2; ++j) mac<C::CHAIN>(acc, d[j], a.v[i - j]);
-    if ((i & 1) == 0) mac<C::CHAIN>(acc, a.v[i / 2], a.v[i / 2]);
-#pragma unroll
-    for (int j = i - NL + 1; j < NL; ++j) mac_k<C::CHAIN>(acc, m[j], C::MOD[i - j]);
-    r.v[i - NL] = (uint32_t)acc & LMASK;
-    acc >>= LB;
-  }
-  r.v[NL - 1] = (uint32_t)acc;
-  return r;
-}
-
-// Two independent Montgomery products / squares in lockstep (the chained columns of both
-// interleave, so a dependent mad of one chain follows an independent mad of the other instead of
-// a wait state).  Same arithmetic as mul() / sqr() on each pair.
-template <class C>
-ZDEV void mul_pair(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c, const Fe<C>& d, Fe<C>& r, Fe<C>& s) {
-  uint32_t m[NL], n[NL];
-  uint64_t x = 0, y = 0;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-#pragma unroll
-    for (int j = 0; j < i; ++j) {
-      mac<C::CHAIN>(x, a.v[j], b.v[i - j]);
-      mac<C::CHAIN>(y, c.v[j], d.v[i - j]);
-      mac_k<C::CHAIN>(x, m[j], C::MOD[i - j]);
-      mac_k<C::CHAIN>(y, n[j], C::MOD[i - j]);
-    }
-    mac<C::CHAIN>(x, a.v[i], b.v[0]);
-    mac<C::CHAIN>(y, c.v[i], d.v[0]);
-    m[i] = ((uint32_t)x * C::INV) & LMASK;
-    n[i] = ((uint32_t)y * C::INV) & LMASK;
-    mac_k<C::CHAIN>(x, m[i], C::MOD[0]);
-    mac_k<C::CHAIN>(y, n[i], C::MOD[0]);
-    x >>= LB;
-    y >>= LB;
-  }
-#pragma unroll
-  for (int i = NL; i < 2 * NL - 1; ++i) {
-#pragma unroll
-    for (int j = i - NL + 1; j < NL; ++j) {
-      mac<C::CHAIN>(x, a.v[j], b.v[i - j]);
-      mac<C::CHAIN>(y, c.v[j], d.v[i - j]);
-      mac_k<C::CHAIN>(x, m[j], C::MOD[i - j]);
-      mac_k<C::CHAIN>(y, n[j], C::MOD[i - j]);
-    }
-    r.v[i - NL] = (uint32_t)x & LMASK;
-    s.v[i - NL] = (uint32_t)y & LMASK;
-    x >>= LB;
-    y >>= LB;
-  }
-  r.v[NL - 1] = (uint32_t)x;
-  s.v[NL - 1] = (uint32_t)y;
-}
-
-// Two lazily reduced sums of N products, r = sum_k a[k] b[k], s = sum_k c[k] d[k], in lockstep with
-// chained columns when CH: the Fq2 products of the G2 arithmetic (c0 and c1 of a product).  Operand
-// conditions as mul2; N = 4: columns hold <= 36 + 9 partial products < 2^58 (< 2^63.5), the sum
-// < ~169 m^2.
-template <class C, bool CH, int N>
-ZDEV void sop_pair(const Fe<C>* const (&a)[N], const Fe<C>* const (&b)[N], const Fe<C>* const (&c)[N],
-                   const Fe<C>* const (&d)[N], Fe<C>& r, Fe<C>& s) {
-  uint32_t m[NL], n[NL];
-  uint64_t x = 0, y = 0;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-#pragma unroll
-    for (int j = 0; j < i; ++j) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) {
-        mac<CH>(x, a[k]->v[j], b[k]->v[i - j]);
-        mac<CH>(y, c[k]->v[j], d[k]->v[i - j]);
-      }
-      mac_k<CH>(x, m[j], C::MOD[i - j]);
-      mac_k<CH>(y, n[j], C::MOD[i - j]);
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      mac<CH>(x, a[k]->v[i], b[k]->v[0]);
-      mac<CH>(y, c[k]->v[i], d[k]->v[0]);
-    }
-    m[i] = ((uint32_t)x * C::INV) & LMASK;
-    n[i] = ((uint32_t)y * C::INV) & LMASK;
-    mac_k<CH>(x, m[i], C::MOD[0]);
-    mac_k<CH>(y, n[i], C::MOD[0]);
-    x >>= LB;
-    y >>= LB;
-  }
-#pragma unroll
-  for (int i = NL; i < 2 * NL - 1; ++i) {
-#pragma unroll
-    for (int j = i - NL + 1; j < NL; ++j) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) {
-        mac<CH>(x, a[k]->v[j], b[k]->v[i - j]);
-        mac<CH>(y, c[k]->v[j], d[k]->v[i - j]);
-      }
-      mac_k<CH>(x, m[j], C::MOD[i - j]);
-      mac_k<CH>(y, n[j], C::MOD[i - j]);
-    }
-    r.v[i - NL] = (uint32_t)x & LMASK;
-    s.v[i - NL] = (uint32_t)y & LMASK;
-    x >>= LB;
-    y >>= LB;
-  }
-  r.v[NL - 1] = (uint32_t)x;
-  s.v[NL - 1] = (uint32_t)y;
-}
-
-template <class C>
-ZDEV void sqr_pair(const Fe<C>& a, const Fe<C>& c, Fe<C>& r, Fe<C>& s) {
-  uint32_t m[NL], n[NL], da[NL], dc[NL];
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-    da[i] = a.v[i] << 1;
-    dc[i] = c.v[i] << 1;
-  }
-  uint64_t x = 0, y = 0;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-#pragma unroll
-    for (int j = 0; j < (i + 1) / 2; ++j) {
-      mac<C::CHAIN>(x, da[j], a.v[i - j]);
-      mac<C::CHAIN>(y, dc[j], c.v[i - j]);
-    }
-    if ((i & 1) == 0) {
-      mac<C::CHAIN>(x, a.v[i / 2], a.v[i / 2]);
-      mac<C::CHAIN>(y, c.v[i / 2], c.v[i / 2]);
-    }
-#pragma unroll
-    for (int j = 0; j < i; ++j) {
-      mac_k<C::CHAIN>(x, m[j], C::MOD[i - j]);
-      mac_k<C::CHAIN>(y, n[j], C::MOD[i - j]);
-    }
-    m[i] = ((uint32_t)x * C::INV) & LMASK;
-    n[i] = ((uint32_t)y * C::INV) & LMASK;
-    mac_k<C::CHAIN>(x, m[i], C::MOD[0]);
-    mac_k<C::CHAIN>(y, n[i], C::MOD[0]);
-    x >>= LB;
-    y >>= LB;
-  }
-#pragma unroll
-  for (int i = NL; i < 2 * NL - 1; ++i) {
-#pragma unroll
-    for (int j = i - NL + 1; j < (i + 1) / 2; ++j) {
-      mac<C::CHAIN>(x, da[j], a.v[i - j]);
-      mac<C::CHAIN>(y, dc[j], c.v[i - j]);
-    }
-    if ((i & 1) == 0) {
-      mac<C::CHAIN>(x, a.v[i / 2], a.v[i / 2]);
-      mac<C::CHAIN>(y, c.v[i / 2], c.v[i / 2]);
-    }
-#pragma unroll
-    for (int j = i - NL + 1; j < NL; ++j) {
-      mac_k<C::CHAIN>(x, m[j], C::MOD[i - j]);
-      mac_k<C::CHAIN>(y, n[j], C::MOD[i - j]);
-    }
-    r.v[i - NL] = (uint32_t)x & LMASK;
-    s.v[i - NL] = (uint32_t)y & LMASK;
-    x >>= LB;
-    y >>= LB;
-  }
-  r.v[NL - 1] = (uint32_t)x;
-  s.v[NL - 1] = (uint32_t)y;
-}
+// ---------------------------------------------------------------- sums and differences
+// A sum or difference is ONE limb pass (add_raw / borrow_sub) followed by one of three tails:
+//   raw         nothing: limbs stay unnormalised
+//   normalized  the carry pass alone: no conditional subtraction
+//   reduce2 / reduce8   down to < 2m from < 4m / < 8m
+// The functions below only name a (table, tail) pair; their comments carry the value bounds.
 
 // carry-propagate limbs 0..7 into 29-bit digits (limb values must be >= 0 and < 2^31)
 template <class C>
@@ -446,6 +270,11 @@ ZDEV void normalize(Fe<C>& a) {
     a.v[i + 1] += a.v[i] >> LB;
     a.v[i] &= LMASK;
   }
+}
+template <class C>
+ZDEV Fe<C> normalized(Fe<C> s) {
+  normalize(s);
+  return s;
 }
 
 // a - M if a >= M else a   (a normalised; M normalised limbs)
@@ -503,38 +332,60 @@ ZDEV Fe<C> reduce2(Fe<C> s) {
   }
 }
 
-// a + b, inputs < 2m (normalised) -> output < 2m
+// x < 8m (normalised) -> < 2m
 template <class C>
-ZDEV Fe<C> add(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + b.v[i];
-  return reduce2(s);
-}
+ZDEV Fe<C> canon8(const Fe<C>& a) { return cond_sub(cond_sub(a, C::MOD4), C::MOD2); }
 
-// a - b, inputs < 2m -> output < 2m   (computes a + 2m - b)
+// s (limbs 0..7 >= 0 and < 2^32 - 2^10, Fq: < 2^31; value in [0, 8m)) -> < 2m (Fr: qreduce, < 1.2m)
 template <class C>
-ZDEV Fe<C> sub(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD2_BORROW[i] - b.v[i];
-  return reduce2(s);
-}
-
-// a - b for a normalised a < 4m and b <= 4m (computes a + 4m - b): output < 2m (Fr: qreduce < 1.2m).
-// The NTT with Shoup root products (outputs < 3m) subtracts with it.
-template <class C>
-ZDEV Fe<C> sub4(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD4_BORROW[i] - b.v[i];
+ZDEV Fe<C> reduce8(Fe<C> s) {
   if constexpr (C::QRED) {
     return qreduce(s);
   } else {
     normalize(s);
-    return cond_sub(cond_sub(s, C::MOD4), C::MOD2);
+    return canon8(s);
   }
 }
+
+// a + b limb by limb, raw: no carry pass, no reduction
+template <class C>
+ZDEV Fe<C> add_raw(const Fe<C>& a, const Fe<C>& b) {
+  Fe<C> s;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + b.v[i];
+  return s;
+}
+
+// a + K - b (- 2c) limb by limb, raw, for a borrow form K of a multiple of m (consts.hpp): K's low
+// limbs are raised by what the subtrahends can reach (MODk_BORROW: 2^29, one normalised b;
+// MOD8_B30: 2^30, a raw sum b; MOD6_WIDE: 2^31, b and 2c normalised) so that no limb 0..7 goes
+// below zero.  The caller names the tail.  K comes as ZTAB(name), a function i -> C::name[i], and
+// not as a reference to the table: device code folds a table into literals only where it is indexed
+// directly; a table bound to a reference stays in memory and its limbs arrive by scalar loads.
+#define ZTAB(K) [](int i) { return C::K[i]; }
+template <class C, class T>
+ZDEV Fe<C> borrow_sub(const Fe<C>& a, T K, const Fe<C>& b, const Fe<C>* c = nullptr) {
+  Fe<C> s;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) {
+    s.v[i] = a.v[i] + K(i) - b.v[i];
+    if (c) s.v[i] -= c->v[i] << 1;
+  }
+  return s;
+}
+
+// a + b, inputs < 2m (normalised) -> output < 2m
+template <class C>
+ZDEV Fe<C> add(const Fe<C>& a, const Fe<C>& b) { return reduce2(add_raw(a, b)); }
+
+// a - b, inputs < 2m -> output < 2m   (computes a + 2m - b)
+template <class C>
+ZDEV Fe<C> sub(const Fe<C>& a, const Fe<C>& b) { return reduce2(borrow_sub(a, ZTAB(MOD2_BORROW), b)); }
+
+// a - b for a normalised a < 4m and b <= 4m (computes a + 4m - b): output < 2m (Fr: qreduce < 1.2m).
+// The NTT with Shoup root products (outputs < 3m) subtracts with it.
+template <class C>
+ZDEV Fe<C> sub4(const Fe<C>& a, const Fe<C>& b) { return reduce8(borrow_sub(a, ZTAB(MOD4_BORROW), b)); }
 
 // ---- lazy subtractions: results that only ever feed a multiplication skip the final
 // conditional subtraction (and, for one mul operand, even the carry normalisation):
@@ -544,23 +395,12 @@ ZDEV Fe<C> sub4(const Fe<C>& a, const Fe<C>& b) {
 
 // a - b + 2m, normalised, value < 4m: an operand of mul() / sqr() only
 template <class C>
-ZDEV Fe<C> lsub(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD2_BORROW[i] - b.v[i];
-  normalize(s);
-  return s;
-}
+ZDEV Fe<C> lsub(const Fe<C>& a, const Fe<C>& b) { return normalized(borrow_sub(a, ZTAB(MOD2_BORROW), b)); }
 
 // a - b + 4m, NOT normalised (every limb in [0, 2^31), value < 6m): ONE operand of
 // mul() whose other operand is normalised; never sqr(), add(), sub(), is_zero(), storage
 template <class C>
-ZDEV Fe<C> rsub(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD4_BORROW[i] - b.v[i];
-  return s;
-}
+ZDEV Fe<C> rsub(const Fe<C>& a, const Fe<C>& b) { return borrow_sub(a, ZTAB(MOD4_BORROW), b); }
 
 // a - b - 2c for a, b, c < 2m (normalised), result < 2m: one limb pass against 6m in the
 // wide borrow form (low limbs + 2^31, so three subtrahends never borrow), one carry
@@ -568,15 +408,7 @@ ZDEV Fe<C> rsub(const Fe<C>& a, const Fe<C>& b) {
 // X3 = R^2 - PPP - 2Q of every XYZZ add in one go (~150 instead of ~250 instructions).
 template <class C>
 ZDEV Fe<C> sub_2x(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD6_WIDE[i] - b.v[i] - (c.v[i] << 1);
-  if constexpr (C::QRED) {
-    return qreduce(s);
-  } else {
-    normalize(s);
-    return cond_sub(cond_sub(s, C::MOD4), C::MOD2);
-  }
+  return reduce8(borrow_sub(a, ZTAB(MOD6_WIDE), b, &c));
 }
 
 // ---- lazily reduced accumulator x (G1 XYZZ additions): X3 = R^2 - PPP - 2Q stays in (0, 8m)
@@ -587,44 +419,19 @@ ZDEV Fe<C> sub_2x(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c) {
 // a - b - 2c + 6m for a, b, c < 2m (normalised): normalised, value in (0, 8m)
 template <class C>
 ZDEV Fe<C> sub_2x8(const Fe<C>& a, const Fe<C>& b, const Fe<C>& c) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD6_WIDE[i] - b.v[i] - (c.v[i] << 1);
-  normalize(s);
-  return s;
+  return normalized(borrow_sub(a, ZTAB(MOD6_WIDE), b, &c));
 }
 
 // a - b + 8m for a < 2m, b < 8m (normalised): normalised, value < 10m -- a mul / sqr operand
 template <class C>
-ZDEV Fe<C> lsub8(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD8_BORROW[i] - b.v[i];
-  normalize(s);
-  return s;
-}
-
-// x < 8m (normalised) -> < 2m
-template <class C>
-ZDEV Fe<C> canon8(const Fe<C>& a) { return cond_sub(cond_sub(a, C::MOD4), C::MOD2); }
+ZDEV Fe<C> lsub8(const Fe<C>& a, const Fe<C>& b) { return normalized(borrow_sub(a, ZTAB(MOD8_BORROW), b)); }
 
 // a - b + 4m (b < 4m) and a - b + 6m (b < 6m), normalised: mul / sqr operands
 template <class C>
-ZDEV Fe<C> lsub4(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD4_BORROW[i] - b.v[i];
-  normalize(s);
-  return s;
-}
+ZDEV Fe<C> lsub4(const Fe<C>& a, const Fe<C>& b) { return normalized(borrow_sub(a, ZTAB(MOD4_BORROW), b)); }
 template <class C>
-ZDEV Fe<C> lsub6(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD6_BORROW[i] - b.v[i];
-  normalize(s);
-  return s;
-}
+ZDEV Fe<C> lsub6(const Fe<C>& a, const Fe<C>& b) { return normalized(borrow_sub(a, ZTAB(MOD6_BORROW), b)); }
+
 // 2a, limbs shifted (raw: limbs < 2^30 for a normalised a): ONE operand of mul()
 template <class C>
 ZDEV Fe<C> shl1_raw(const Fe<C>& a) {
@@ -635,33 +442,17 @@ ZDEV Fe<C> shl1_raw(const Fe<C>& a) {
 }
 
 // ---- lazy radix-4 sums (NTT): a first-stage sum x + y of two normalised values < 2m is kept
-// raw (limbs < 2^30, value < 4m, no carry pass and no conditional subtraction); the second
+// raw (add_raw: limbs < 2^30, value < 4m, no carry pass and no conditional subtraction); the second
 // stage consumes two such sums:
 
 // a + b for raw sums a, b < 4m: normalised and reduced from < 8m to < 2m
 template <class C>
-ZDEV Fe<C> add_raw_reduce(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + b.v[i];
-  if constexpr (C::QRED) {
-    return qreduce(s);
-  } else {
-    normalize(s);
-    return cond_sub(cond_sub(s, C::MOD4), C::MOD2);
-  }
-}
+ZDEV Fe<C> add_raw_reduce(const Fe<C>& a, const Fe<C>& b) { return reduce8(add_raw(a, b)); }
 
 // a - b + 6m for raw sums a, b < 4m (wide borrow form: every limb stays >= 0), normalised,
 // value < 10m: an operand of mul() against a normalised value < 2m only (product < 20 m^2)
 template <class C>
-ZDEV Fe<C> sub_raw6(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD6_WIDE[i] - b.v[i];
-  normalize(s);
-  return s;
-}
+ZDEV Fe<C> sub_raw6(const Fe<C>& a, const Fe<C>& b) { return normalized(borrow_sub(a, ZTAB(MOD6_WIDE), b)); }
 
 // a - b + 8m for raw sums a, b < 6m of two normalised values each (limbs < 2^30), WITHOUT a carry
 // pass: the 8m borrow form whose low limbs are raised by 2^30 (consts MOD8_B30) keeps every limb
@@ -672,20 +463,7 @@ ZDEV Fe<C> sub_raw6(const Fe<C>& a, const Fe<C>& b) {
 // raised form keeps 0x1832270 there, so it stays >= 0 for every a (round 6, ADVICE r5: the 6m form's
 // 0x12259d4 wrapped below zero for a ~ 0 against b ~ 6m; tools/hosttest r4lazy covers that quad)
 template <class C>
-ZDEV Fe<C> sub_raw6n(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + C::MOD8_B30[i] - b.v[i];
-  return s;
-}
-
-template <class C>
-ZDEV Fe<C> add_raw(const Fe<C>& a, const Fe<C>& b) {
-  Fe<C> s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + b.v[i];
-  return s;
-}
+ZDEV Fe<C> sub_raw8(const Fe<C>& a, const Fe<C>& b) { return borrow_sub(a, ZTAB(MOD8_B30), b); }
 
 template <class C>
 ZDEV Fe<C> dbl(const Fe<C>& a) { return add(a, a); }
@@ -801,25 +579,19 @@ struct Fq2 {
 
 // 4m - a, normalised, for a normalised a <= 4m (Fq2 components are < 4m: rsub's)
 ZDEV Fq neg4(const Fq& a) {
-  Fq s;
-#pragma unroll
-  for (int i = 0; i < NL; ++i) s.v[i] = FqCfg::MOD4_BORROW[i] - a.v[i];
-  normalize(s);
-  return s;
+  using C = FqCfg;
+  return normalized(borrow_sub(fe_zero<C>(), ZTAB(MOD4_BORROW), a));
 }
 
 // (a0 + a1 u)(b0 + b1 u) = (a0 b0 - a1 b1) + (a0 b1 + a1 b0) u as two lazily reduced sums
 // of products (2 x 162 + 2 x 81 mads, like Karatsuba's 3 x 162, but no Karatsuba adds and
 // subtractions: ~650 instead of ~1100 instructions).  Components normalised, < 4m.
-// The two components' sums of products run in lockstep with chained columns (sop_pair): the 2-wave
-// G2 kernels gain with paired chains (profiles/g2_chain_r03.txt).
+// The two components' sums of products are the two lanes of one mont_sop with chained columns: the
+// 2-wave G2 kernels gain with paired chains (profiles/g2_chain_r03.txt).
 ZDEV Fq2 mul(const Fq2& a, const Fq2& b) {
   Fq2 r;
   const Fq nb1 = neg4(b.c1);
-  const Fq* x0[2] = {&a.c0, &a.c1};
-  const Fq* y0[2] = {&b.c0, &nb1};
-  const Fq* y1[2] = {&b.c1, &b.c0};
-  sop_pair<FqCfg, true, 2>(x0, y0, x0, y1, r.c0, r.c1);
+  mont_sop<FqCfg, true, 2, 2>({{&a.c0, &a.c1}, {&a.c0, &a.c1}}, {{&b.c0, &nb1}, {&b.c1, &b.c0}}, {&r.c0, &r.c1});
   return r;
 }
 
@@ -827,10 +599,8 @@ ZDEV Fq2 mul(const Fq2& a, const Fq2& b) {
 ZDEV Fq2 mul2(const Fq2& a, const Fq2& b, const Fq2& c, const Fq2& d) {
   Fq2 r;
   const Fq nb1 = neg4(b.c1), nd1 = neg4(d.c1);
-  const Fq* x[4] = {&a.c0, &a.c1, &c.c0, &c.c1};
-  const Fq* y0[4] = {&b.c0, &nb1, &d.c0, &nd1};
-  const Fq* y1[4] = {&b.c1, &b.c0, &d.c1, &d.c0};
-  sop_pair<FqCfg, true, 4>(x, y0, x, y1, r.c0, r.c1);
+  mont_sop<FqCfg, true, 2, 4>({{&a.c0, &a.c1, &c.c0, &c.c1}, {&a.c0, &a.c1, &c.c0, &c.c1}},
+                              {{&b.c0, &nb1, &d.c0, &nd1}, {&b.c1, &b.c0, &d.c1, &d.c0}}, {&r.c0, &r.c1});
   return r;
 }
 
@@ -854,12 +624,8 @@ ZDEV Fq2 lsub4_lazy(const Fq2& a, const Fq2& b) { return Fq2{lsub4(a.c0, b.c0), 
 // (2 a0) a1 [raw x normalised, < 72 m^2] -- no additions reduced, no doubling of the product
 ZDEV Fq2 sqr_lazy(const Fq2& a) {
   const Fq s = add_raw(a.c0, a.c1), d = lsub6(a.c0, a.c1), t = shl1_raw(a.c0);
-  const Fq* x0[1] = {&s};
-  const Fq* y0[1] = {&d};
-  const Fq* x1[1] = {&t};
-  const Fq* y1[1] = {&a.c1};
   Fq2 r;
-  sop_pair<FqCfg, true, 1>(x0, y0, x1, y1, r.c0, r.c1);
+  mont_sop<FqCfg, true, 2, 1>({{&s}, {&t}}, {{&d}, {&a.c1}}, {&r.c0, &r.c1});
   return r;
 }
 // R^2 - PPP - 2Q per component (each < 2m) -> < 4m: one conditional subtraction instead of two.
@@ -872,10 +638,11 @@ ZDEV Fq2 sub_2x4(const Fq2& a, const Fq2& b, const Fq2& c) {
 ZDEV Fq2 canon4(const Fq2& a) { return Fq2{cond_sub(a.c0, FqCfg::MOD2), cond_sub(a.c1, FqCfg::MOD2)}; }
 
 ZDEV Fq2 add(const Fq2& a, const Fq2& b) { return Fq2{add(a.c0, b.c0), add(a.c1, b.c1)}; }
-// Fq2 lazy forms: Karatsuba mul() adds the components of each operand, so a raw
-// (unnormalised) operand is not allowed; a normalised < 4m one is (sums < 6m after add's
-// conditional subtraction, products < 24 m^2 < m R').  sqr() subtracts components, so
-// its operand stays canonical: lsub = sub.
+// The generic (non-accumulator) lazy names on Fq2, as the doubling formulas of curve.hpp use them.
+// An Fq2 mul() / mul2() is a sum of several products per component, so EVERY operand must be
+// normalised (no raw operand as in the one-product Fq mul), and neg4 wants the second operand's c1
+// <= 4m: rsub is therefore the normalised lsub per component (< 4m).  sqr() reduces its operand's
+// components with add() / sub(), which take values < 2m: lsub is the fully reduced sub.
 ZDEV Fq2 sub_2x(const Fq2& a, const Fq2& b, const Fq2& c) {
   return Fq2{sub_2x(a.c0, b.c0, c.c0), sub_2x(a.c1, b.c1, c.c1)};
 }

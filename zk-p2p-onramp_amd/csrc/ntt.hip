@@ -139,11 +139,12 @@ __device__ __forceinline__ Fr root_mul(const Fr& a, uint32_t j, const uint32_t* 
 // (span H) and t+1 (span H/2), r0 = grp 2H + i.
 // Value bounds (round 5, host-tested: tools/hosttest op r4lazy): every tile value between rounds is
 // normalised (limbs < 2^29) and < 3m (Shoup outputs < 3m, qreduce outputs < 1.2m).  The first-stage
-// sums stay raw (< 6m, limbs < 2^30); their difference takes the 2^30-raised 6m borrow form without a
-// carry pass (sub_raw6n: limbs < 2.5 * 2^30, < 12m), a mul_shoup operand.  RAW: the unit is the last
-// one of a DFT whose outputs only feed a Montgomery product (the DIF pass's inter-pass twiddle, the
-// coset key between the fused kernel's two DFTs): its four outputs stay unreduced (< 12m, limbs
-// < 2.5 * 2^30 -- a mul() operand against the normalised table value), 4 reductions fewer.
+// sums stay raw (< 6m, limbs < 2^30); their difference takes the 2^30-raised 8m borrow form without a
+// carry pass (sub_raw8: limbs < 2.5 * 2^30, < 6m + 8m = 14m), a mul_shoup operand.  RAW: the unit is the
+// last one of a DFT whose outputs only feed a Montgomery product (the DIF pass's inter-pass twiddle, the
+// coset key between the fused kernel's two DFTs): its four outputs stay unreduced (< 14m, limbs
+// < 2.5 * 2^30 -- a mul() operand against the normalised table value < 2m: 28 m^2, far below the
+// 169 m^2 that keeps a product < 2m, field.hpp mont_sop), 4 reductions fewer.
 template <int LE>
 __device__ __forceinline__ void r4_unit(uint32_t* __restrict__ lds, const uint32_t* __restrict__ ltw, int E, int b,
                                         int lc, int t, int q, bool raw) {
@@ -179,18 +180,18 @@ __device__ __forceinline__ void r4_unit(uint32_t* __restrict__ lds, const uint32
   if (Hh > 1) {
     lds_put<LE>(lds, E, p0, add_raw_reduce(s02, s13));
     Fr y1, y3;
-    root_mul_pair(sub_raw6n(s02, s13), j, rsub(d02, d13), j, ltw, y1, y3);
+    root_mul_pair(sub_raw8(s02, s13), j, rsub(d02, d13), j, ltw, y1, y3);
     lds_put<LE>(lds, E, p1, y1);
     lds_put<LE>(lds, E, p3, y3);
     lds_put<LE>(lds, E, p2, add(d02, d13));
   } else if (raw) {  // last pair (span 1, no multiply in stage t+1), outputs into a Montgomery product
     lds_put<LE>(lds, E, p0, add_raw(s02, s13));    // < 12m, limbs < 2^31
-    lds_put<LE>(lds, E, p1, sub_raw6n(s02, s13));  // < 12m, limbs < 2.5 * 2^30
+    lds_put<LE>(lds, E, p1, sub_raw8(s02, s13));   // < 14m, limbs < 2.5 * 2^30
     lds_put<LE>(lds, E, p2, add_raw(d02, d13));    // < 6m, limbs < 2^30
     lds_put<LE>(lds, E, p3, rsub(d02, d13));       // < 7m, limbs < 1.5 * 2^30
   } else {  // last pair, outputs stored: one reduction each
     lds_put<LE>(lds, E, p0, add_raw_reduce(s02, s13));
-    lds_put<LE>(lds, E, p1, qreduce(sub_raw6n(s02, s13)));
+    lds_put<LE>(lds, E, p1, qreduce(sub_raw8(s02, s13)));
     lds_put<LE>(lds, E, p2, add(d02, d13));
     lds_put<LE>(lds, E, p3, stage_sub(d02, d13));
   }
