@@ -103,7 +103,7 @@ zkp_status zkp_zkey_contribute(int device, const uint8_t* zkey, size_t len, cons
  * draws the rest of the contribution from the same stream (G1.fromRng, the transcript, hashToG2),
  * applies k on the GPU and appends the type-1 record (deltaAfter, proof of knowledge,
  * transcript, numIterationsExp, beacon hash, name) to section 10, so the key passes `zkey
- * verify` (reference circuit/scripts/generate_keys_phase2_groth16.sh:26).  e <= 63; name may be
+ * verify` (zkp_zkey_verify; reference circuit/scripts/generate_keys_phase2_groth16.sh:26).  e <= 63; name may be
  * NULL (not recorded).  Record bytes restated (oracle/mpc.py), parity unpinned. */
 zkp_status zkp_beacon_secret(const uint8_t* beacon, size_t len, uint32_t num_iterations_exp, uint8_t* k32);
 zkp_status zkp_zkey_beacon(int device, const uint8_t* zkey, size_t len, const uint8_t* beacon, size_t beacon_len,
@@ -132,6 +132,38 @@ zkp_status zkp_blake2b512(const uint8_t* data, size_t len, uint8_t* out64);
  * points and the ptau's tauG1 powers, host).  *out: the zkey (zkp_buffer_free). */
 zkp_status zkp_zkey_new(int device, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
                         uint8_t** out, size_t* out_len);
+
+/* Setup acceleration: `snarkjs zkey verify`, the gate of every phase-2 ceremony (reference
+ * circuit/scripts/generate_keys_phase2_groth16.sh:26, circuit/server-scripts/
+ * generate_keys_phase2_groth16.sh:56, generate_chunked_keys_phase2_groth16.sh:68,
+ * zk-email-verify-circuits/scripts/compile.js:109), against the initial key `zkey new` wrote for the same
+ * circuit and ptau.  The checks of oracle/mpc.py zkey_verify in its order and words: the transcript
+ * chain of every contribution (transcript hash, hashToG2, the two same-ratio pairings, the beacon's
+ * re-draw), the header, delta1, delta2, the csHash, sections 3-7 byte for byte (host); then L and H
+ * as random linear combinations of both keys' sections on `device`, one pairing check each.  Also,
+ * with messages of their own: every point of sections 2 and 10 is on its curve (G2: in the subgroup)
+ * and every L / H point is canonical and on the curve ("INVALID: L section point <i> is not on the
+ * curve": the smallest such i).
+ * The status reports only malformed input (ZKP_ERR_FORMAT, ...) or a device error.  A key that fails
+ * a check is ZKP_OK with *valid = 0 and the failing check in msg ("OK" and *valid = 1 otherwise); msg
+ * (may be NULL) receives at most msg_cap - 1 characters and a NUL.
+ * seed32 seeds the linear combinations' coefficients (128-bit: a wrong section passes with
+ * probability <= 2^-128 each).  PRODUCTION MUST PASS NULL (32 bytes from the OS CSPRNG): the
+ * coefficients must be unpredictable to whoever wrote the key.  Non-NULL is for reproducible tests.
+ * ZKP_VERIFY_CHUNK=<points> (default 4194304) sets the points per device chunk; a malformed value or
+ * one below 1 is a ZKP_ERR_INVALID_ARG.  Messages restated (oracle/mpc.py), parity unpinned. */
+zkp_status zkp_zkey_verify_frominit(int device, const uint8_t* init, size_t init_len, const uint8_t* key, size_t key_len,
+                                    const uint8_t* seed32 /* NULL: OS CSPRNG (production) */, int* valid,
+                                    char* msg, size_t msg_cap);
+/* `snarkjs zkey verify <r1cs> <ptau> <zkey>`: zkp_zkey_new on `device`, then the above. */
+zkp_status zkp_zkey_verify(int device, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
+                           const uint8_t* key, size_t key_len, const uint8_t* seed32, int* valid, char* msg, size_t msg_cap);
+/* ms of the last zkp_zkey_verify[_frominit] on this thread: [0] total, [1] host (parsing, transcript
+ * chain, pairings), [2] the section compares, then the L and H linear combinations together:
+ * [3] upload (host wall; overlaps the previous chunk's compute), [4] point check, [5] coefficient
+ * generation, [6] base conversion + plan, [7] [8] accumulate + finish over the initial / the checked
+ * key's points, [9] host folds, [10] their wall time, [11] chunks.  n = capacity of ms. */
+zkp_status zkp_zkey_verify_timings(double* ms, int n);
 
 /* Load only point slice `part` of `nparts` (contiguous ranges of the witness-indexed
  * sections 5-8 and of section 9) onto one device.  Such a prover computes partial sums
@@ -243,6 +275,19 @@ zkp_status zkp_msm_g2(int device, const uint8_t* points, const uint8_t* scalars,
  * one bucket set; 1 = no precomputed rows, one bucket group per window). */
 zkp_status zkp_msm(int device, int g2, const uint8_t* points, const uint8_t* scalars, size_t n, int window_bits,
                    int table_depth, uint8_t* out, int* is_inf);
+/* The device parts of zkp_zkey_verify, each on its own.
+ * zkp_rlc_coeffs: coefficients first_index .. first_index + n - 1 of a verification, generated on the
+ * device: coefficient i is the 128-bit LE integer of outputs 4i..4i+3 (lowest word first) of
+ * ffjavascript's ChaCha word stream seeded with the 8 big-endian 32-bit words of seed32.  out: n x 16
+ * bytes LE.  One stream serves a verification: L takes 0..nL-1, H takes nL..nL+nH-1.
+ * zkp_points_check: *n_bad = the points (zkey layout; g2: 128 bytes each) that have a coordinate >= p
+ * or are neither all-zero nor on the curve; *first_bad = the smallest such index (UINT64_MAX if none).
+ * zkp_rlc_g1: sum_i coeff(first_index + i) * a_i and the same over b_i (G1, zkey layout) under one
+ * MSM plan, after zkp_points_check of both (a bad point is a ZKP_ERR_INVALID_ARG). */
+zkp_status zkp_rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_index, size_t n, uint8_t* out);
+zkp_status zkp_points_check(int device, int g2, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad);
+zkp_status zkp_rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* points_a,
+                      const uint8_t* points_b, size_t n, uint8_t* out_a64, int* inf_a, uint8_t* out_b64, int* inf_b);
 /* In-place Fr transforms on n = 2^k standard-form LE elements, natural order:
  * mode 0: forward (A_j = sum a_i w^ij), 1: inverse, 2: coset-extend (snarkjs
  * ifft -> batchApplyKey(1, Fr.w[k+1]) -> fft). */

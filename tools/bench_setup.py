@@ -42,11 +42,65 @@ def sections(buf: bytes):
     return out
 
 
+def verify_bench(res, z0: bytes, z2: bytes):
+    """--verify: `zkey verify` (zkp_zkey_verify_frominit, a fresh random seed) of the final key against the
+    initial one with its split, the verdict on a copy with two adjacent L points swapped, and the route
+    the library offered before for the same four sums: four zkp_msm_g1 calls over the L / H sections of
+    both keys with the same coefficients widened to 32-byte scalars, default parameters (their time
+    includes each call's base-table build; generating the coefficients is not counted)."""
+    import ctypes
+    import numpy as np
+    seed = os.urandom(32)
+    t0 = time.time()
+    ok, msg = zkp_amd.zkey_verify_frominit(z0, z2, seed=seed)
+    res["zkey_verify_s"] = round(time.time() - t0, 3)
+    res["zkey_verify"] = {"valid": ok, "message": msg}
+    res["valid"] = ok
+    res["zkey_verify_split_ms"] = {k: round(v, 2) for k, v in zkp_amd.zkey_verify_timings().items()}
+    sec0, sec2 = sections(z0), sections(z2)
+    off, ln = sec2[8]
+    bad = bytearray(z2)
+    assert bad[off:off + 64] != bad[off + 64:off + 128]
+    bad[off:off + 64], bad[off + 64:off + 128] = bad[off + 64:off + 128], bad[off:off + 64]
+    bad = bytes(bad)
+    t0 = time.time()
+    ok_bad, msg_bad = zkp_amd.zkey_verify_frominit(z0, bad, seed=seed)
+    res["zkey_verify_swapped_l"] = {"valid": ok_bad, "message": msg_bad, "s": round(time.time() - t0, 3)}
+    del bad
+    # the four-MSM route
+    lib = zkp_amd.load_library()
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    n_l, n_h = sec0[8][1] // 64, sec0[9][1] // 64
+    sp = ctypes.cast(ctypes.c_char_p(seed), u8p)
+    sums, total = {}, 0.0
+    for name, sid, first, n in (("L", 8, 0, n_l), ("H", 9, n_l, n_h)):
+        c16 = np.zeros((n, 16), dtype=np.uint8)
+        st = lib.zkp_rlc_coeffs(0, sp, first, n, c16.ctypes.data_as(u8p))
+        assert st == 0, st
+        c32 = np.zeros((n, 32), dtype=np.uint8)
+        c32[:, :16] = c16
+        scal = c32.tobytes()
+        del c16, c32
+        for tag, z, sec in (("init", z0, sec0), ("key", z2, sec2)):
+            o, ln = sec[sid]
+            pts = bytes(memoryview(z)[o:o + ln])
+            t0 = time.time()
+            sums[name + "_" + tag] = zkp_amd.msm_g1(pts, scal)
+            dt = time.time() - t0
+            del pts
+            res.setdefault("four_msm_g1_s", {})[name + "_" + tag] = round(dt, 3)
+            total += dt
+    res["four_msm_g1_s"]["total"] = round(total, 3)
+    res["four_msm_g1_sums_finite"] = all(v is not None for v in sums.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the Venmo shape")
     ap.add_argument("--out", default="")
     ap.add_argument("--cpu-check", action="store_true", help="prove with oracle/cpu too (about 15 s on 16 cores)")
+    ap.add_argument("--verify", action="store_true",
+                    help="time `zkey verify` of the final key against the initial one, and the four-MSM route")
     args = ap.parse_args()
     v = synth.VENMO
     circ = synth.Circuit(int(v["n_vars"] * args.scale), int(v["n_constraints"] * args.scale), v["n_public"],
@@ -85,6 +139,8 @@ def main():
     res["zkey_beacon_s"] = round(time.time() - t0, 3)
     res["total_s"] = round(res["zkey_new_s"] + res["zkey_contribute_s"] + res["zkey_beacon_s"], 3)
     res["zkey_bytes"] = len(z2)
+    if args.verify:
+        verify_bench(res, z0, z2)
     del z0, z1
     wit = circ.witness(4242)
     p = zkp_amd.Prover(z2, devices=[0])

@@ -19,12 +19,14 @@
 
 #include "../../include/zkp_amd.h"
 #include "beacon.hpp"
+#include "device_pipeline.hpp"
 #include "hip_check.hpp"
 #include "host_ec.hpp"
 #include "host_pairing.hpp"
 #include "mpc.hpp"
 #include "prover.hpp"
 #include "zkey_io.hpp"
+#include "zkey_verify.hpp"
 
 static_assert(sizeof(zkp_partial) == 392, "zkp_partial is exchanged as 392 raw bytes");
 
@@ -333,6 +335,89 @@ zkp_status zkp_zkey_new(int device, const uint8_t* r1cs, size_t r1cs_len, const 
   std::vector<uint8_t> buf;
   zkp_status s = guard([&] { buf = zkp::zkey_new(device, r1cs, r1cs_len, ptau, ptau_len); });
   return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+}  // extern "C"
+
+namespace {
+thread_local zkp::VerifyTimings g_verify_timings;
+
+// the verdict's message into the caller's buffer (truncated to msg_cap - 1 characters)
+void put_msg(const std::string& m, char* msg, size_t msg_cap) {
+  if (!msg || !msg_cap) return;
+  const size_t n = std::min(m.size(), msg_cap - 1);
+  std::memcpy(msg, m.data(), n);
+  msg[n] = 0;
+}
+}  // namespace
+extern "C" {
+
+zkp_status zkp_zkey_verify_frominit(int device, const uint8_t* init, size_t init_len, const uint8_t* key,
+                                    size_t key_len, const uint8_t* seed32, int* valid, char* msg, size_t msg_cap) {
+  if (!init || !init_len || !key || !key_len || !valid) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  *valid = 0;
+  put_msg("", msg, msg_cap);
+  return guard([&] {
+    std::string m;
+    *valid = zkp::zkey_verify_frominit(device, init, init_len, key, key_len, seed32, m, &g_verify_timings) ? 1 : 0;
+    put_msg(m, msg, msg_cap);
+  });
+}
+
+zkp_status zkp_zkey_verify(int device, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
+                           const uint8_t* key, size_t key_len, const uint8_t* seed32, int* valid, char* msg,
+                           size_t msg_cap) {
+  if (!r1cs || !r1cs_len || !ptau || !ptau_len || !key || !key_len || !valid)
+    return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  *valid = 0;
+  put_msg("", msg, msg_cap);
+  return guard([&] {
+    {  // a malformed key fails before the initial key is built on the device
+      const zkp::ZkeyParsed z = zkp::parse_zkey(key, key_len, false);
+      if (!z.bf.sec[10].ptr) throw zkp::ZkpError(ZKP_ERR_FORMAT, "zkey: missing section 10 (MPC parameters)");
+      (void)zkp::read_mpc(z.bf.sec[10].ptr, z.bf.sec[10].len);
+    }
+    const std::vector<uint8_t> init = zkp::zkey_new(device, r1cs, r1cs_len, ptau, ptau_len);
+    std::string m;
+    *valid = zkp::zkey_verify_frominit(device, init.data(), init.size(), key, key_len, seed32, m, &g_verify_timings) ? 1 : 0;
+    put_msg(m, msg, msg_cap);
+  });
+}
+
+zkp_status zkp_zkey_verify_timings(double* ms, int n) {
+  if (!ms || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const zkp::VerifyTimings& t = g_verify_timings;
+  const double v[12] = {t.total_ms,      t.host_ms,         t.compare_ms,      t.rlc.upload_ms,
+                        t.rlc.check_ms,  t.rlc.coeffs_ms,   t.rlc.plan_ms,     t.rlc.acc_ms[0],
+                        t.rlc.acc_ms[1], t.rlc.fold_ms,     t.rlc.total_ms,    (double)t.rlc.chunks};
+  for (int i = 0; i < n && i < 12; ++i) ms[i] = v[i];
+  return ZKP_OK;
+}
+
+zkp_status zkp_rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_index, size_t n, uint8_t* out) {
+  if (!seed32 || (n && !out)) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::rlc_coeffs(device, seed32, first_index, n, out); });
+}
+
+zkp_status zkp_points_check(int device, int g2, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad) {
+  if ((n && !points) || !n_bad || !first_bad) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::points_check(device, g2 != 0, points, n, n_bad, first_bad); });
+}
+
+zkp_status zkp_rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* points_a,
+                      const uint8_t* points_b, size_t n, uint8_t* out_a64, int* inf_a, uint8_t* out_b64, int* inf_b) {
+  if (!seed32 || (n && (!points_a || !points_b)) || !out_a64 || !inf_a || !out_b64 || !inf_b)
+    return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] {
+    const zkp::RlcResult r = zkp::rlc_g1(device, seed32, first_index, points_a, points_b, n);
+    if (r.first_bad_a != zkp::RLC_NO_BAD || r.first_bad_b != zkp::RLC_NO_BAD)
+      throw zkp::ZkpError(ZKP_ERR_INVALID_ARG,
+                          std::string("rlc: point ") +
+                              std::to_string(r.first_bad_a != zkp::RLC_NO_BAD ? r.first_bad_a : r.first_bad_b) +
+                              (r.first_bad_a != zkp::RLC_NO_BAD ? " of set a" : " of set b") + " is not on the curve");
+    *inf_a = zkp::jac_to_bytes_g1(r.sum_a, out_a64) ? 0 : 1;
+    *inf_b = zkp::jac_to_bytes_g1(r.sum_b, out_b64) ? 0 : 1;
+  });
 }
 
 zkp_status zkp_prover_load_part(const uint8_t* zkey, size_t len, int device, int part, int nparts,

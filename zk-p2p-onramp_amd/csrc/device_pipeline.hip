@@ -131,9 +131,9 @@ MsmOptions msm_options() {
   return o;
 }
 
-MsmParams make_params(size_t n, int c, int depth) {
+MsmParams make_params(size_t n, int c, int depth, int scalar_bits) {
   try {
-    return MsmParams::make(n, c, depth);
+    return MsmParams::make(n, c, depth, scalar_bits);
   } catch (const std::invalid_argument& x) {
     throw ZkpError(ZKP_ERR_INVALID_ARG, x.what());
   }

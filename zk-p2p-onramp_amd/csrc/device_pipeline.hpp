@@ -63,7 +63,7 @@ struct MsmOptions {
 MsmOptions msm_options();
 
 // MsmParams::make with its std::invalid_argument as a ZKP_ERR_INVALID_ARG
-MsmParams make_params(size_t n, int c, int depth);
+MsmParams make_params(size_t n, int c, int depth, int scalar_bits = 255);
 
 // the task size (task = the plan's task_w / task_h option, 0: the default of 48 entries) and the
 // reduction segment (seg=) of a plan.

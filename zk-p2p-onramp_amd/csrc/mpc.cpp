@@ -2,10 +2,15 @@
 #include "mpc.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
+#include <fstream>
 #include <thread>
 
+#include "beacon.hpp"
+#include "host_pairing.hpp"
 #include "prover.hpp"
+#include "zkey_verify.hpp"
 
 namespace zkp {
 
@@ -604,6 +609,204 @@ void binfile_replace_section(std::vector<uint8_t>& file, uint32_t id, const std:
     out[11] = (uint8_t)((nsec + 1) >> 24);
   }
   file.swap(out);
+}
+
+// ---------------------------------------------------------------- zkey verify
+namespace {
+
+// e(g1a, g2b) == e(g1b, g2a); false if any point is the point at infinity
+bool same_ratio(const Affine<HFq>& g1a, const Affine<HFq>& g1b, const Affine<HFq2>& g2a, const Affine<HFq2>& g2b) {
+  if (g1a.inf || g1b.inf || g2a.inf || g2b.inf) return false;
+  const Affine<HFq> ps[2] = {Affine<HFq>{g1a.x, g1a.y.neg(), false}, g1b};
+  const Affine<HFq2> qs[2] = {g2b, g2a};
+  return host::fq12_is_one(host::final_exponentiation(host::miller_loop_multi(ps, qs, 2)));
+}
+template <class F>
+bool same_point(const Affine<F>& a, const Affine<F>& b) {
+  return a.inf == b.inf && (a.inf || (a.x == b.x && a.y == b.y));
+}
+bool g2_valid(const Affine<HFq2>& p) { return host::g2_on_curve(p) && host::g2_in_subgroup(p); }
+
+Affine<HFq2> g2_generator() {  // Verifier.sol:33-36
+  auto fq = [](const char* dec) {
+    U256 v{{0, 0, 0, 0}};
+    for (const char* c = dec; *c; ++c) {
+      host::u128 carry = (host::u128)(*c - '0');
+      for (int i = 0; i < 4; ++i) {
+        const host::u128 t = (host::u128)v.w[i] * 10 + carry;
+        v.w[i] = (host::u64)t;
+        carry = t >> 64;
+      }
+    }
+    return HFq::from_std(v);
+  };
+  return Affine<HFq2>{HFq2{fq("10857046999023057135944570762232829481370756359578518086990519993285655852781"),
+                           fq("11559732032986387107991004021392285783925812861821192530917403151452391805634")},
+                      HFq2{fq("8495653923123431417604973247489272438418190587263600148770280649306958101930"),
+                           fq("4082367875863433681332203403145435568316851327593401208105741076214120093531")},
+                      false};
+}
+
+// the beacon parameters of a contribution's parameter bytes (1: name, 2: numIterationsExp, one value
+// byte, 3: beacon hash), every length bounded by the bytes present
+struct BeaconParams {
+  bool has_exp = false, has_hash = false;
+  uint32_t exp = 0;
+  std::vector<uint8_t> hash;
+};
+BeaconParams parse_contribution_params(const std::vector<uint8_t>& prm) {
+  BeaconParams b;
+  size_t j = 0;
+  while (j < prm.size()) {
+    const uint8_t pid = prm[j];
+    if (prm.size() - j < 2) throw ZkpError(ZKP_ERR_FORMAT, "zkey: section 10 parameter is truncated");
+    if (pid == 2) {
+      b.has_exp = true;
+      b.exp = prm[j + 1];
+      j += 2;
+      continue;
+    }
+    if (pid != 1 && pid != 3) throw ZkpError(ZKP_ERR_FORMAT, "zkey: MPC parameter " + std::to_string(pid) + " not recognized");
+    const size_t ln = prm[j + 1];
+    if (prm.size() - j - 2 < ln) throw ZkpError(ZKP_ERR_FORMAT, "zkey: section 10 parameter is truncated");
+    if (pid == 3) {
+      b.has_hash = true;
+      b.hash.assign(prm.begin() + j + 2, prm.begin() + j + 2 + ln);
+    }
+    j += 2 + ln;
+  }
+  return b;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+bool zkey_verify_frominit(int device, const uint8_t* init, size_t init_len, const uint8_t* key, size_t key_len,
+                          const uint8_t* seed32, std::string& msg, VerifyTimings* timings) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  VerifyTimings tm;
+  auto verdict = [&](bool ok, const std::string& m) {
+    msg = m;
+    tm.total_ms = ms_since(t_begin);
+    if (timings) *timings = tm;
+    return ok;
+  };
+  auto bad = [&](const std::string& m) { return verdict(false, m); };
+  auto tag = [](size_t i) { return "INVALID(" + std::to_string(i) + "): "; };
+
+  const ZkeyParsed zk = parse_zkey(key, key_len, false), z0 = parse_zkey(init, init_len, false);
+  const Section* s = zk.bf.sec;
+  const Section* s0 = z0.bf.sec;
+  if (!s[10].ptr) throw ZkpError(ZKP_ERR_FORMAT, "zkey: missing section 10 (MPC parameters)");
+  if (!s0[10].ptr) throw ZkpError(ZKP_ERR_FORMAT, "initial zkey: missing section 10 (MPC parameters)");
+  const MpcParams mpc = read_mpc(s[10].ptr, s[10].len), mpc0 = read_mpc(s0[10].ptr, s0[10].len);
+  // the parameter bytes of every contribution, as the oracle's reader takes them before any check
+  std::vector<BeaconParams> params;
+  for (size_t i = 0; i < mpc.contributions.size(); ++i) {
+    params.push_back(parse_contribution_params(mpc.contributions[i].params));
+    if (mpc.contributions[i].type != 1) continue;
+    if (!params[i].has_exp || !params[i].has_hash)
+      throw ZkpError(ZKP_ERR_FORMAT, "zkey: section 10 beacon contribution " + std::to_string(i) + " has no beacon parameters");
+    // 2^e chained hashes: the bound `zkey beacon` itself accepts
+    if (params[i].exp > 63) throw ZkpError(ZKP_ERR_FORMAT, "zkey: section 10 beacon numIterationsExp must be <= 63");
+  }
+  const Affine<HFq> g1gen{fq_small(1), fq_small(2), false};
+  const Affine<HFq2> g2gen = g2_generator();
+
+  // 1. the transcript chain of every contribution
+  Blake2b acc;
+  acc.update(mpc.cs_hash, 64);
+  Affine<HFq> cur = g1gen;
+  for (size_t i = 0; i < mpc.contributions.size(); ++i) {
+    const MpcContribution& c = mpc.contributions[i];
+    if (!host::g1_on_curve(c.delta_after) || !host::g1_on_curve(c.g1_s) || !host::g1_on_curve(c.g1_sx))
+      return bad(tag(i) + "a G1 point of the contribution is not on the curve");
+    if (!g2_valid(c.g2_spx)) return bad(tag(i) + "the G2 point of the contribution is not in G2");
+    Blake2b th = acc;
+    hash_g1(th, c.g1_s);
+    hash_g1(th, c.g1_sx);
+    uint8_t digest[64];
+    th.final(digest);
+    if (std::memcmp(digest, c.transcript, 64) != 0) return bad(tag(i) + "inconsistent transcript");
+    const Affine<HFq2> g2_sp = hash_to_g2(c.transcript);
+    if (!same_ratio(c.g1_s, c.g1_sx, g2_sp, c.g2_spx))
+      return bad(tag(i) + "public key G1 and G2 do not have the same ratio");
+    if (!same_ratio(cur, c.delta_after, g2_sp, c.g2_spx)) return bad(tag(i) + "deltaAfter does not follow the public key");
+    const BeaconParams bp = parse_contribution_params(c.params);  // bounded again where its values are used
+    if (c.type == 1) {
+      if (!bp.has_exp || !bp.has_hash)
+        throw ZkpError(ZKP_ERR_FORMAT, "zkey: beacon contribution " + std::to_string(i) + " has no beacon parameters");
+      if (bp.exp > 63) throw ZkpError(ZKP_ERR_FORMAT, "zkey: beacon numIterationsExp must be <= 63");
+      uint8_t h[32];
+      beacon_hash(bp.hash.data(), bp.hash.size(), bp.exp, h);
+      uint32_t seed[8];
+      seed_from_hash(h, seed);
+      ChaChaRng rng(seed);
+      const HFr k = fr_from_rng(rng);
+      const Affine<HFq> g1_s = g1_from_rng(rng);
+      if (!same_point(g1_s, c.g1_s) || !same_point(g1_times(g1_s, k.to_std()), c.g1_sx))
+        return bad(tag(i) + "does not match the beacon");
+    }
+    hash_pubkey(acc, c);
+    cur = c.delta_after;
+  }
+  // 2. the header against the initial key (its points checked first: section 2 is input too)
+  const ZkeyHeader& h = zk.hdr;
+  const ZkeyHeader& h0 = z0.hdr;
+  if (!host::g1_on_curve(h.alpha1) || !host::g1_on_curve(h.beta1) || !host::g1_on_curve(h.delta1))
+    return bad("INVALID: a G1 point of the header is not on the curve");
+  if (!g2_valid(h.beta2) || !g2_valid(h.gamma2) || !g2_valid(h.delta2))
+    return bad("INVALID: a G2 point of the header is not in G2");
+  if (!g2_valid(h0.delta2)) throw ZkpError(ZKP_ERR_FORMAT, "initial zkey: delta2 is not in G2");
+  auto differs = [&](const char* f) { return bad(std::string("INVALID: ") + f + " differs from the initial key"); };
+  if (h.n_vars != h0.n_vars) return differs("n_vars");
+  if (h.n_public != h0.n_public) return differs("n_public");
+  if (h.domain_size != h0.domain_size) return differs("domain_size");
+  if (!same_point(h.alpha1, h0.alpha1)) return differs("alpha1");
+  if (!same_point(h.beta1, h0.beta1)) return differs("beta1");
+  if (!same_point(h.beta2, h0.beta2)) return differs("beta2");
+  if (!same_point(h.gamma2, h0.gamma2)) return differs("gamma2");
+  // 3., 4. delta
+  if (!same_point(h.delta1, cur)) return bad("INVALID: delta1 is not the last deltaAfter");
+  if (!same_ratio(g1gen, cur, g2gen, h.delta2)) return bad("INVALID: delta2");
+  // 5. csHash
+  if (std::memcmp(mpc.cs_hash, mpc0.cs_hash, 64) != 0) return bad("INVALID: circuit does not match (csHash)");
+  tm.host_ms = ms_since(t_begin);
+  // 6. the sections no contribution touches
+  const auto t_cmp = std::chrono::steady_clock::now();
+  for (int id : {3, 4, 5, 6, 7})
+    if (s[id].len != s0[id].len || (s[id].len && std::memcmp(s[id].ptr, s0[id].ptr, s[id].len) != 0))
+      return bad("INVALID: section " + std::to_string(id) + " is not identical to the initial key's");
+  tm.compare_ms = ms_since(t_cmp);
+  // 7. L, then H: new = old * delta_init / delta
+  uint8_t seed[32];
+  if (seed32) {
+    std::memcpy(seed, seed32, 32);
+  } else {
+    std::ifstream f("/dev/urandom", std::ios::binary);
+    if (!f.read(reinterpret_cast<char*>(seed), 32)) throw ZkpError(ZKP_ERR_IO, "cannot read /dev/urandom");
+  }
+  uint64_t first_index = 0;
+  for (int id : {8, 9}) {
+    const std::string name = id == 8 ? "L" : "H";
+    if (s[id].len != s0[id].len) return bad("INVALID: " + name + " section size");
+    const size_t count = s[id].len / 64;
+    const RlcResult r = rlc_g1(device, seed, first_index, s0[id].ptr, s[id].ptr, count);
+    first_index += count;
+    tm.rlc.add(r.t);
+    if (r.first_bad_b != RLC_NO_BAD)
+      return bad("INVALID: " + name + " section point " + std::to_string(r.first_bad_b) + " is not on the curve");
+    if (r.first_bad_a != RLC_NO_BAD)
+      return bad("INVALID: initial key's " + name + " section point " + std::to_string(r.first_bad_a) +
+                 " is not on the curve");
+    // e(sum r_i old_i, delta2) == e(sum r_i new_i, delta2_init)
+    if (!same_ratio(host::jac_to_aff(r.sum_a), host::jac_to_aff(r.sum_b), h.delta2, h0.delta2))
+      return bad("INVALID: " + name + " section is not the initial one times delta^-1");
+  }
+  return verdict(true, "OK");
 }
 
 }  // namespace zkp

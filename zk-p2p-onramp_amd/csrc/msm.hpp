@@ -53,12 +53,18 @@ struct MsmParams {
   int S = 32;        // max entries per accumulate task
   int S2 = 4;        // fan-in of a heavy-bucket merge level (short chains: latency-bound)
   int M = 4;         // buckets per reduction segment (running sums)
+  // bits the windows cover: 255 = any scalar below r plus the signed-digit carry.  A caller whose
+  // scalars are all below 2^b passes b + 1 and gets ceil((b + 1) / c) windows: no digits, buckets or
+  // reductions for the windows above (zkey_verify.hip: 128-bit coefficients, 129)
+  int scalar_bits = 255;
   // c_override / depth_override: 0 = automatic.  Window bits must lie in [MIN_C, MAX_C]: W <= 32
   // windows keep a scalar block's digits in one LDS stage of the bucket sort, and the bucket key
   // (group and bucket bits, <= 27) splits into its three passes (hsort_kernels.hpp).
   static constexpr int MIN_C = 8, MAX_C = 24;
-  static MsmParams make(size_t n, int c_override = 0, int depth_override = 0) {
+  static MsmParams make(size_t n, int c_override = 0, int depth_override = 0, int scalar_bits = 255) {
     MsmParams p;
+    if (scalar_bits < 1 || scalar_bits > 255) throw std::invalid_argument("MSM scalar bits must be within 1..255");
+    p.scalar_bits = scalar_bits;
     int lg = 0;
     while ((size_t(1) << lg) < n) ++lg;
     // one bucket set of 2^(c-1) buckets against n*W entries: c = lg - 4 keeps every bucket ~8*W
@@ -67,7 +73,7 @@ struct MsmParams {
     if (p.c < MIN_C || p.c > MAX_C)
       throw std::invalid_argument("MSM window bits must be within " + std::to_string(MIN_C) + ".." +
                                   std::to_string(MAX_C) + " (got " + std::to_string(p.c) + ")");
-    p.windows = (255 + p.c - 1) / p.c;
+    p.windows = (scalar_bits + p.c - 1) / p.c;
     p.depth = depth_override > 0 ? (depth_override < p.windows ? depth_override : p.windows) : p.windows;
     p.groups = (p.windows + p.depth - 1) / p.depth;
     if (p.M > (1 << (p.c - 1))) p.M = 1 << (p.c - 1);

@@ -12,15 +12,18 @@
  * a contribution and the final beacon (3_gen_chunk_zkey.sh:27,36; the record is appended to section 10):
  *   node cli.js zkey contribute <in.zkey> <out.zkey> -e=<entropy> [-n=name]
  *   node cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]
+ * and the gate of the ceremony (reference circuit/scripts/generate_keys_phase2_groth16.sh:26):
+ *   node cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>
  */
 const fs = require('fs');
-const { groth16, exportSolidityCallData, newZKey, beacon, contribute, release } = require('./groth16');
+const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, release } = require('./groth16');
 
 const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n' +
               '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
               '       cli.js groth16 setup|zkey new <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>\n' +
               '       cli.js zkey contribute <in.zkey> <out.zkey> -e=<entropy> [-n=name]\n' +
-              '       cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]\n';
+              '       cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]\n' +
+              '       cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n';
 
 async function main(argv) {
   if (argv.length === 5 && argv[0] === 'zkey' && argv[1] === 'export' && argv[2] === 'soliditycalldata') {
@@ -35,6 +38,15 @@ async function main(argv) {
     return 0;
   }
   const named = argv.filter((a) => !/^(-n|--name)=/.test(a) && a !== '-v' && a !== '--verbose');
+  if (named.length === 5 && argv[0] === 'zkey' && argv[1] === 'verify') {
+    // snarkjs' log lines (recalled from snarkjs 0.4.22, unpinned): "[INFO]  snarkJS: ZKey Ok!" and exit 0,
+    // else the reason and "[ERROR] snarkJS: Invalid zkey" and exit 1
+    const logger = {
+      info: (m) => process.stdout.write(`[INFO]  snarkJS: ${m}\n`),
+      error: (m) => process.stdout.write(`[ERROR] snarkJS: ${m}\n`),
+    };
+    return (await verifyFromR1cs(named[2], named[3], named[4], logger)) ? 0 : 1;
+  }
   if (argv[0] === 'zkey' && argv[1] === 'contribute') {
     const pos = argv.filter((a) => !a.startsWith('-'));
     const ent = argv.find((a) => /^(-e|--entropy)=/.test(a));

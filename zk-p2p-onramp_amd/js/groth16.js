@@ -215,6 +215,39 @@ async function contribute(zkeyNameOld, zkeyNameNew, name, entropy, logger, devic
   return out;
 }
 
+/*
+ * snarkjs' `zKey.verifyFromR1cs(r1csName, ptauName, zkeyName, logger)` (the `zkey verify` gate of a
+ * ceremony, reference circuit/scripts/generate_keys_phase2_groth16.sh:26): the initial key is rebuilt
+ * on the GPU (`zkey new`) and the key checked against it (the transcript chain on the host, the L / H
+ * sections as random linear combinations on the GPU).  Resolves to a boolean as snarkjs does; the
+ * failing check goes to logger.error, "ZKey Ok!" to logger.info (strings recalled from snarkjs
+ * 0.4.22, unpinned).  Malformed input rejects.
+ */
+function reportVerdict(res, logger) {
+  if (logger) {
+    if (res.valid && logger.info) logger.info('ZKey Ok!');
+    if (!res.valid && logger.error) {
+      logger.error(res.message);
+      logger.error('Invalid zkey');
+    }
+  }
+  return res.valid;
+}
+async function verifyFromR1cs(r1csName, ptauName, zkeyName, logger, device) {
+  return reportVerdict(addon.zkeyVerifyFromR1cs(readInput(r1csName), readInput(ptauName), readInput(zkeyName),
+                                                device || 0), logger);
+}
+/*
+ * `zKey.verifyFromInit(initName, zkeyName, logger)`: the same against an initial key at hand.  snarkjs'
+ * own shape (initName, ptauName, zkeyName, logger) is accepted too; the ptau is not needed, the H
+ * section is compared against the initial key's.
+ */
+async function verifyFromInit(initName, zkeyName, logger, device, ...rest) {
+  const isInput = (x) => typeof x === 'string' || (x && typeof x === 'object' && x.type === 'mem');
+  if (isInput(logger)) return verifyFromInit(initName, logger, device, ...rest);
+  return reportVerdict(addon.zkeyVerify(readInput(initName), readInput(zkeyName), device || 0), logger);
+}
+
 function release() {
   for (const h of provers.values()) addon.freeProver(h);
   for (const h of memProvers.values()) addon.freeProver(h);
@@ -225,7 +258,9 @@ function release() {
 module.exports = {
   groth16: { prove, proveBatch },
   proveBatch,
-  zKey: { exportSolidityCallData, newZKey, beacon, contribute },
+  zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit },
+  verifyFromR1cs,
+  verifyFromInit,
   newZKey,
   beacon,
   contribute,

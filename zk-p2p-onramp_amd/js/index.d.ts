@@ -30,7 +30,18 @@ export declare const zKey: {
   /** `snarkjs zkey beacon`'s group arithmetic on the GPU (no transcript record appended) */
   beacon(zkeyNameOld: Input, zkeyNameNew: string | { type: "mem"; data?: Uint8Array } | undefined, name: string,
          beaconHashStr: string, numIterationsExp: number, logger?: Logger, device?: number): Promise<Buffer>;
+  /** `snarkjs zkey verify <r1cs> <ptau> <zkey>`: the initial key rebuilt on the GPU, the key checked against
+   *  it (L / H on the GPU); the failing check goes to logger.error.  Malformed input rejects. */
+  verifyFromR1cs(r1csName: Input, ptauName: Input, zkeyName: Input, logger?: VerifyLogger, device?: number):
+    Promise<boolean>;
+  /** the same against the initial key `zkey new` wrote */
+  verifyFromInit(initName: Input, zkeyName: Input, logger?: VerifyLogger, device?: number): Promise<boolean>;
 };
+export interface VerifyLogger extends Logger { error?(msg: string): void }
+export declare function verifyFromR1cs(r1csName: Input, ptauName: Input, zkeyName: Input, logger?: VerifyLogger,
+                                       device?: number): Promise<boolean>;
+export declare function verifyFromInit(initName: Input, zkeyName: Input, logger?: VerifyLogger, device?: number):
+  Promise<boolean>;
 export declare function exportSolidityCallData(proof: Proof, publicSignals: string[]): Promise<string>;
 export declare function onRampArgs(proof: Proof, publicSignals: string[]):
   [[string, string], [[string, string], [string, string]], [string, string], string[]];

@@ -12,6 +12,8 @@
  *   zkeyNew(r1csBuffer, ptauBuffer, device?)     -> Buffer (`snarkjs zkey new`, synchronous)
  *   zkeyBeacon(zkeyBuffer, beaconBuffer, numIterationsExp, device?, name?) -> Buffer (`zkey beacon`)
  *   zkeyContribute(zkeyBuffer, entropy, name?, device?) -> Buffer (`zkey contribute`)
+ *   zkeyVerify(initBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify` against the initial key)
+ *   zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify`)
  *   version()
  * prove()/proveBatch() run on the libuv threadpool (napi_async_work), so the JS main
  * thread is never blocked — the same async contract as snarkjs' Promise API.
@@ -115,6 +117,51 @@ static napi_value js_zkey_new(napi_env env, napi_callback_info info) {
     return NULL;
   }
   return buf;
+}
+
+/* zkeyVerify(initBuffer, zkeyBuffer, device?) / zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer,
+ * device?) -> {valid: boolean, message: string}: `snarkjs zkey verify` (zkp_zkey_verify_frominit /
+ * zkp_zkey_verify, coefficients seeded by the OS CSPRNG), synchronous -- a setup step.  Malformed
+ * input throws with the zkp_status as code. */
+static napi_value verify_common(napi_env env, napi_callback_info info, int nbuf, const char* usage) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void* p[3] = {NULL, NULL, NULL};
+  size_t len[3] = {0, 0, 0};
+  bool ok = argc >= (size_t)nbuf;
+  for (int i = 0; ok && i < nbuf; ++i) {
+    bool b = false;
+    napi_is_buffer(env, argv[i], &b);
+    ok = b && napi_get_buffer_info(env, argv[i], &p[i], &len[i]) == napi_ok;
+  }
+  if (!ok) {
+    napi_throw_type_error(env, NULL, usage);
+    return NULL;
+  }
+  int device = 0;
+  if (argc > (size_t)nbuf) napi_get_value_int32(env, argv[nbuf], &device);
+  int valid = 0;
+  char msg[256];
+  zkp_status st =
+      nbuf == 2 ? zkp_zkey_verify_frominit(device, (const uint8_t*)p[0], len[0], (const uint8_t*)p[1], len[1], NULL,
+                                           &valid, msg, sizeof msg)
+                : zkp_zkey_verify(device, (const uint8_t*)p[0], len[0], (const uint8_t*)p[1], len[1],
+                                  (const uint8_t*)p[2], len[2], NULL, &valid, msg, sizeof msg);
+  if (st != ZKP_OK) return throw_status(env, st);
+  napi_value res, v, m;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  NAPI_CALL(env, napi_get_boolean(env, valid != 0, &v));
+  NAPI_CALL(env, napi_create_string_utf8(env, msg, NAPI_AUTO_LENGTH, &m));
+  NAPI_CALL(env, napi_set_named_property(env, res, "valid", v));
+  NAPI_CALL(env, napi_set_named_property(env, res, "message", m));
+  return res;
+}
+static napi_value js_zkey_verify(napi_env env, napi_callback_info info) {
+  return verify_common(env, info, 2, "zkeyVerify(initBuffer, zkeyBuffer, device?)");
+}
+static napi_value js_zkey_verify_r1cs(napi_env env, napi_callback_info info) {
+  return verify_common(env, info, 3, "zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?)");
 }
 
 /* a JS string argument into buf (NULL when absent / undefined / not a string) */
@@ -595,6 +642,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"zkeyNew", NULL, js_zkey_new, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyBeacon", NULL, js_zkey_beacon, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyContribute", NULL, js_zkey_contribute, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyVerify", NULL, js_zkey_verify, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyVerifyFromR1cs", NULL, js_zkey_verify_r1cs, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

@@ -147,6 +147,19 @@ def load_library(path: str = LIB_PATH):
             lib.zkp_prover_get_verify.argtypes = [P, ctypes.POINTER(ctypes.c_int)]
         lib.zkp_proof_verify.argtypes = [u8p, sz, ctypes.POINTER(_Proof), ctypes.POINTER(ctypes.c_int)]
         lib.zkp_pairing.argtypes = [u8p, u8p, u8p]
+        if hasattr(lib, "zkp_zkey_verify_frominit"):  # zkey verify (an older library loads for A/B runs)
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            ip = ctypes.POINTER(ctypes.c_int)
+            lib.zkp_zkey_verify_frominit.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, u8p, ip, ctypes.c_char_p, sz]
+            lib.zkp_zkey_verify.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, u8p, sz, u8p, ip, ctypes.c_char_p, sz]
+            lib.zkp_zkey_verify_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+            lib.zkp_rlc_coeffs.argtypes = [ctypes.c_int, u8p, ctypes.c_uint64, sz, u8p]
+            lib.zkp_points_check.argtypes = [ctypes.c_int, ctypes.c_int, u8p, sz, u64p, u64p]
+            lib.zkp_rlc_g1.argtypes = [ctypes.c_int, u8p, ctypes.c_uint64, u8p, u8p, sz, u8p, ip, u8p, ip]
+        for name in ("zkp_zkey_verify_frominit", "zkp_zkey_verify", "zkp_zkey_verify_timings", "zkp_rlc_coeffs",
+                     "zkp_points_check", "zkp_rlc_g1"):
+            if hasattr(lib, name):
+                getattr(lib, name).restype = ctypes.c_int
         for name in ("zkp_zkey_beacon_named", "zkp_zkey_contribute_entropy", "zkp_blake2b512", "zkp_prover_set_verify", "zkp_prover_get_verify", "zkp_proof_verify", "zkp_pairing", "zkp_prover_load_mem", "zkp_prover_load_file", "zkp_prover_info", "zkp_prove",
                      "zkp_prove_batch", "zkp_prove_batch_status", "zkp_prove_files", "zkp_proof_json", "zkp_public_json",
                      "zkp_prover_timings", "zkp_msm_g1", "zkp_msm_g2", "zkp_ntt_fr", "zkp_quotient",
@@ -626,6 +639,97 @@ def zkey_new(r1cs: bytes, ptau: bytes, device: int = 0) -> bytes:
         return _copy_out(out, n.value)
     finally:
         lib.zkp_buffer_free(out)
+
+
+def _seed(seed):
+    if seed is None:
+        return None, None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("seed must be 32 bytes")
+    return _buf(seed)
+
+
+VERIFY_MSG_CAP = 256
+
+
+def zkey_verify_frominit(init: bytes, key: bytes, seed: bytes = None, device: int = 0):
+    """`snarkjs zkey verify` of `key` against `init`, the key `zkey new` wrote for the same circuit and
+    ptau (zkp_zkey_verify_frominit) -> (valid, message): (True, "OK") or (False, the failing check).
+    The L / H sections are checked on the GPU.  seed (32 bytes) fixes the coefficients of their linear
+    combinations for reproducible tests; production passes None (the OS CSPRNG): the coefficients must
+    be unpredictable to whoever wrote the key.  Malformed input raises ZkpError."""
+    lib = load_library()
+    ip, ilen, ik = _in(init)
+    kp, klen, kk = _in(key)
+    sp, sk = _seed(seed)
+    ok = ctypes.c_int()
+    msg = ctypes.create_string_buffer(VERIFY_MSG_CAP)
+    _check(lib.zkp_zkey_verify_frominit(device, ip, ilen, kp, klen, sp, ctypes.byref(ok), msg, VERIFY_MSG_CAP))
+    return bool(ok.value), msg.value.decode()
+
+
+def zkey_verify(r1cs: bytes, ptau: bytes, key: bytes, seed: bytes = None, device: int = 0):
+    """`snarkjs zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>` (zkp_zkey_verify): zkey_new on the
+    GPU, then zkey_verify_frominit -> (valid, message)."""
+    lib = load_library()
+    rp, rlen, rk = _in(r1cs)
+    pp, plen, pk = _in(ptau)
+    kp, klen, kk = _in(key)
+    sp, sk = _seed(seed)
+    ok = ctypes.c_int()
+    msg = ctypes.create_string_buffer(VERIFY_MSG_CAP)
+    _check(lib.zkp_zkey_verify(device, rp, rlen, pp, plen, kp, klen, sp, ctypes.byref(ok), msg, VERIFY_MSG_CAP))
+    return bool(ok.value), msg.value.decode()
+
+
+def zkey_verify_timings() -> dict:
+    """ms of the calling thread's last zkey_verify / zkey_verify_frominit (zkp_zkey_verify_timings)."""
+    out = (ctypes.c_double * 12)()
+    _check(load_library().zkp_zkey_verify_timings(out, 12))
+    keys = ["total", "host_transcript_pairings", "section_compares", "upload", "point_check", "coeff_gen", "plan",
+            "accumulate_init", "accumulate_key", "host_fold", "lincomb_wall", "chunks"]
+    return dict(zip(keys, list(out)))
+
+
+def rlc_coeffs(seed: bytes, first_index: int, n: int, device: int = 0):
+    """Kernel-level: coefficients first_index .. first_index + n - 1 of a verification seeded with `seed`
+    (32 bytes), generated on the GPU (zkp_rlc_coeffs) -> n ints below 2^128."""
+    sp, sk = _seed(seed)
+    out = (ctypes.c_uint8 * (16 * max(1, n)))()
+    _check(load_library().zkp_rlc_coeffs(device, sp, first_index, n, ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8))))
+    raw = bytes(out)
+    return [_le(raw[16 * i:16 * i + 16]) for i in range(n)]
+
+
+def points_check(points_lem: bytes, g2: bool = False, device: int = 0):
+    """Kernel-level: (bad, first_bad) over zkey-layout points (zkp_points_check): how many have a
+    coordinate >= p or are neither all-zero nor on the curve, and the smallest such index (None if 0)."""
+    pp, pk = _buf(bytes(points_lem) or b"\0")
+    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
+    n = len(points_lem) // (128 if g2 else 64)
+    _check(load_library().zkp_points_check(device, 1 if g2 else 0, pp, n, ctypes.byref(bad), ctypes.byref(first)))
+    return bad.value, (first.value if bad.value else None)
+
+
+def rlc_g1(seed: bytes, first_index: int, points_a: bytes, points_b: bytes, device: int = 0):
+    """Kernel-level: the two linear combinations sum_i coeff(first_index + i) * P_i over two G1 point
+    sets of one size under one MSM plan (zkp_rlc_g1) -> ((x, y) or None, (x, y) or None)."""
+    if len(points_a) != len(points_b):
+        raise ValueError("the two point sets must have one size")
+    sp, sk = _seed(seed)
+    ap, ak = _buf(bytes(points_a) or b"\0")
+    bp, bk = _buf(bytes(points_b) or b"\0")
+    oa, ob = (ctypes.c_uint8 * 64)(), (ctypes.c_uint8 * 64)()
+    ia, ib = ctypes.c_int(), ctypes.c_int()
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    _check(load_library().zkp_rlc_g1(device, sp, first_index, ap, bp, len(points_a) // 64, ctypes.cast(oa, u8p),
+                                     ctypes.byref(ia), ctypes.cast(ob, u8p), ctypes.byref(ib)))
+
+    def pt(raw, inf):
+        raw = bytes(raw)
+        return None if inf.value else (_le(raw[:32]), _le(raw[32:]))
+    return pt(oa, ia), pt(ob, ib)
 
 
 def _proof_struct(proof, public_signals):
