@@ -5,6 +5,7 @@
 #include <cstring>
 #include <string>
 #include "../../zk-p2p-onramp_amd/csrc/curve.hpp"
+#include "../../zk-p2p-onramp_amd/csrc/ntt_unit.hpp"
 using namespace zkp;
 
 static void rd(uint32_t w[8]) { for (int i = 0; i < 8; ++i) if (scanf("%x", &w[i]) != 1) exit(1); }
@@ -32,6 +33,13 @@ template <class C> static void mul_shoup_pair_op() {  // per lane: a (limbs), w 
   mul_shoup_pair(a, w, wq, c, v, vq, r, s);
   prf(r); printf("\n"); prf(s); printf("\n"); prf(mul_shoup(a, w, wq)); printf("\n"); prf(mul_shoup(c, v, vq));
 }
+
+// ntt_unit.hpp's root hooks with one root for every exponent
+struct HostRoots {
+  Fr w, wq;
+  void pair(const Fr& a, uint32_t, const Fr& c, uint32_t, Fr& r, Fr& s) const { mul_shoup_pair(a, w, wq, c, w, wq, r, s); }
+  Fr one(const Fr& a, uint32_t) const { return mul_shoup(a, w, wq); }
+};
 
 int main() {
   char op[32];
@@ -65,23 +73,31 @@ int main() {
       // w plain root (words) with its Shoup quotient wq (limbs), tw a table value < 2m (words)
       Fr x0 = rdf<FrCfg>(), x1 = rdf<FrCfg>(), x2 = rdf<FrCfg>(), x3 = rdf<FrCfg>(), w = rdf<FrCfg>();
       Fr wq = rdl<FrCfg>(), tw = rdf<FrCfg>();
+      // the units themselves (csrc/ntt_unit.hpp, the text ntt.hip expands), every root = w
+      const HostRoots rt{w, wq};
+      Fr f[4], lr[4], ls[4], o[4], br[2];
+      r4_arith(x0, x1, x2, x3, 0u, 2u, 0, false, rt, [&](int k, const Fr& y) { f[k] = y; });   // Hh > 1
+      r4_arith(x0, x1, x2, x3, 0u, 1u, 0, true, rt, [&](int k, const Fr& y) { lr[k] = y; });   // last pair, raw
+      r4_arith(x0, x1, x2, x3, 0u, 1u, 0, false, rt, [&](int k, const Fr& y) { ls[k] = y; });  // last pair, stored
+      r2_first(x0, x1, 0u, rt, [&](int k, const Fr& y) { o[k] = y; });                         // odd b's first stage
+      r2_last(x0, x2, true, [&](int k, const Fr& y) { br[k] = y; });                           // b == 1, raw
       const Fr s02 = add_raw(x0, x2), s13 = add_raw(x1, x3);
-      prf(mul_shoup(sub_raw8(s02, s13), w, wq)); printf("\n");    // full unit: y1 (< 3m)
-      prf(qreduce(sub_raw8(s02, s13))); printf("\n");             // stored last pair: p1 (< 1.2m)
-      prf(mul(add_raw(s02, s13), tw)); printf("\n");              // raw last pair p0 x twiddle (< 2m)
-      prf(mul(sub_raw8(s02, s13), tw)); printf("\n");             // raw p1 x twiddle
-      prf(mul(add_raw(x0, x2), tw)); printf("\n");                // raw p2 (d02 + d13, each < 3m)
-      prf(mul(rsub(x0, x2), tw)); printf("\n");                   // raw p3 / odd stage x - y + 4m
+      prf(f[1]); printf("\n");                                    // full unit: y1 = (s02 - s13) w (< 3m)
+      prf(ls[1]); printf("\n");                                   // stored last pair: p1 (< 1.2m)
+      prf(mul(lr[0], tw)); printf("\n");                          // raw last pair p0 x twiddle (< 2m)
+      prf(mul(lr[1], tw)); printf("\n");                          // raw p1 x twiddle
+      prf(mul(br[0], tw)); printf("\n");                          // b == 1 raw p0 = x0 + x2
+      prf(mul(br[1], tw)); printf("\n");                          // b == 1 raw p1 / odd stage x - y + 4m
       // last pair (Hh == 1): d02 = x0 - x2 by the root w^0, only reduced; d13 a Shoup product
       const Fr d02 = qreduce(rsub(x0, x2)), d13 = mul_shoup(rsub(x1, x3), w, wq);
       prf(d02); printf("\n");                                       // < 1.2m
-      prf(add(d02, d13)); printf("\n");                             // stored p2
-      prf(sub4(d02, d13)); printf("\n");                            // stored p3 (stage_sub)
-      prf(mul(add_raw(d02, d13), tw)); printf("\n");               // raw p2 x twiddle
-      prf(mul(rsub(d02, d13), tw)); printf("\n");                   // raw p3 x twiddle
+      prf(ls[2]); printf("\n");                                     // stored p2
+      prf(ls[3]); printf("\n");                                     // stored p3 (stage_sub)
+      prf(mul(lr[2], tw)); printf("\n");                            // raw p2 x twiddle
+      prf(mul(lr[3], tw)); printf("\n");                            // raw p3 x twiddle
       // odd b's first radix-2 stage (span 2^(b-1)): x0 + x1 and (x0 - x1) w
-      prf(add(x0, x1)); printf("\n");
-      prf(mul_shoup(rsub(x0, x1), w, wq)); printf("\n");
+      prf(o[0]); printf("\n");
+      prf(o[1]); printf("\n");
       // raw last-round outputs into the Shoup twiddle / coset-key products (round 5 tables)
       prf(mul_shoup(add_raw(s02, s13), w, wq)); printf("\n");
       prf(mul_shoup(add_raw(x0, x2), w, wq)); printf("\n");

@@ -35,11 +35,11 @@ struct FConst<Fe<C>> {
   static ZDEV Fe<C> zero() { return fe_zero<C>(); }
   static ZDEV Fe<C> one() { return fe_one<C>(); }
 };
-template <>
-struct FConst<Fq2> {
+template <class C>
+struct FConst<Fq2T<C>> {
   static constexpr bool LOCKSTEP = false;
-  static ZDEV Fq2 zero() { return Fq2{fe_zero<FqCfg>(), fe_zero<FqCfg>()}; }
-  static ZDEV Fq2 one() { return Fq2{fe_one<FqCfg>(), fe_zero<FqCfg>()}; }
+  static ZDEV Fq2T<C> zero() { return Fq2T<C>{fe_zero<C>(), fe_zero<C>()}; }
+  static ZDEV Fq2T<C> one() { return Fq2T<C>{fe_one<C>(), fe_zero<C>()}; }
 };
 template <class F>
 ZDEV F f_zero() { return FConst<F>::zero(); }
@@ -53,29 +53,37 @@ ZDEV F f_one() { return FConst<F>::one(); }
 //  G2: x < 4m (one conditional subtraction per component instead of two), P, R < 6m / 4m
 //      without conditional subtractions, squares of such values by sqr_lazy; the Y3 sum of
 //      products puts the < 6m factor first (Fq2 mul2 negates the SECOND factor's c1, which must
-//      stay <= 4m).  Bounds: field.hpp, host-tested (tools/hosttest).
+//      stay <= 4m).  Bounds: field.hpp; proven for every input, with the invariant closing over each
+//      of the functions below, by tools/hosttest/bounds.cpp.
 template <class C>
 ZDEV Fe<C> acc_x3(const Fe<C>& rr, const Fe<C>& ppp, const Fe<C>& q) { return sub_2x8(rr, ppp, q); }
-ZDEV Fq2 acc_x3(const Fq2& rr, const Fq2& ppp, const Fq2& q) { return sub_2x4(rr, ppp, q); }
+template <class C>
+ZDEV Fq2T<C> acc_x3(const Fq2T<C>& rr, const Fq2T<C>& ppp, const Fq2T<C>& q) { return sub_2x4(rr, ppp, q); }
 template <class C>
 ZDEV Fe<C> acc_xsub(const Fe<C>& a, const Fe<C>& x) { return lsub8(a, x); }  // a - x for an accumulator x
-ZDEV Fq2 acc_xsub(const Fq2& a, const Fq2& x) { return lsub4_lazy(a, x); }
+template <class C>
+ZDEV Fq2T<C> acc_xsub(const Fq2T<C>& a, const Fq2T<C>& x) { return lsub4_lazy(a, x); }
 template <class C>
 ZDEV Fe<C> acc_sub(const Fe<C>& a, const Fe<C>& b) { return lsub(a, b); }  // a - b, both < 2m
-ZDEV Fq2 acc_sub(const Fq2& a, const Fq2& b) { return lsub2_lazy(a, b); }
+template <class C>
+ZDEV Fq2T<C> acc_sub(const Fq2T<C>& a, const Fq2T<C>& b) { return lsub2_lazy(a, b); }
 template <class C>
 ZDEV Fe<C> acc_sqr(const Fe<C>& a) { return sqr(a); }  // a < 11m
-ZDEV Fq2 acc_sqr(const Fq2& a) { return sqr_lazy(a); }  // components < 6m
+template <class C>
+ZDEV Fq2T<C> acc_sqr(const Fq2T<C>& a) { return sqr_lazy(a); }  // components < 6m
 template <class C>
 ZDEV Fe<C> acc_negd(const Fe<C>& a) { return rsub(fe_zero<C>(), a); }
-ZDEV Fq2 acc_negd(const Fq2& a) { return lsub2_lazy(Fq2{fe_zero<FqCfg>(), fe_zero<FqCfg>()}, a); }
+template <class C>
+ZDEV Fq2T<C> acc_negd(const Fq2T<C>& a) { return lsub2_lazy(Fq2T<C>{fe_zero<C>(), fe_zero<C>()}, a); }
 // Y3 = R T + Y D (T = Q - X3, D = -PPP)
 template <class C>
 ZDEV Fe<C> acc_y3(const Fe<C>& r, const Fe<C>& t, const Fe<C>& y, const Fe<C>& d) { return mul2(r, t, y, d); }
-ZDEV Fq2 acc_y3(const Fq2& r, const Fq2& t, const Fq2& y, const Fq2& d) { return mul2(t, r, d, y); }
+template <class C>
+ZDEV Fq2T<C> acc_y3(const Fq2T<C>& r, const Fq2T<C>& t, const Fq2T<C>& y, const Fq2T<C>& d) { return mul2(t, r, d, y); }
 template <class C>
 ZDEV Fe<C> acc_xcanon(const Fe<C>& x) { return canon8(x); }
-ZDEV Fq2 acc_xcanon(const Fq2& x) { return canon4(x); }
+template <class C>
+ZDEV Fq2T<C> acc_xcanon(const Fq2T<C>& x) { return canon4(x); }
 
 // independent products of the mixed addition in lockstep: a chained field config (C::CHAIN) runs
 // each pair with interleaved column chains (field.hpp mul_pair / sqr_pair); otherwise, and for Fq2,
@@ -116,10 +124,12 @@ ZDEV bool xyzz_is_inf(const Xyzz<F>& p) { return is_zero_raw(p.zz); }
 // for a normalised a < 2m to be 0 or m (is_zero)
 template <class C>
 ZDEV bool lo_zero(const Fe<C>& a) { return a.v[0] == 0; }
-ZDEV bool lo_zero(const Fq2& a) { return a.c0.v[0] == 0 && a.c1.v[0] == 0; }
+template <class C>
+ZDEV bool lo_zero(const Fq2T<C>& a) { return a.c0.v[0] == 0 && a.c1.v[0] == 0; }
 template <class C>
 ZDEV bool maybe_zero(const Fe<C>& a) { return a.v[0] == 0 || a.v[0] == C::MOD[0]; }
-ZDEV bool maybe_zero(const Fq2& a) { return maybe_zero(a.c0) && maybe_zero(a.c1); }
+template <class C>
+ZDEV bool maybe_zero(const Fq2T<C>& a) { return maybe_zero(a.c0) && maybe_zero(a.c1); }
 
 template <class F>
 ZDEV bool aff_is_inf(const Aff<F>& p) { return is_zero_raw(p.x) && is_zero_raw(p.y); }
@@ -286,13 +296,15 @@ ZDEV Aff<F> xyzz_to_aff(const Xyzz<F>& p) {
 
 template <class C>
 ZDEV void load_f(const uint32_t* p, Fe<C>& x) { x = load_fe<C>(p); }
-ZDEV void load_f(const uint32_t* p, Fq2& x) {
-  x.c0 = load_fe<FqCfg>(p);
-  x.c1 = load_fe<FqCfg>(p + 8);
+template <class C>
+ZDEV void load_f(const uint32_t* p, Fq2T<C>& x) {
+  x.c0 = load_fe<C>(p);
+  x.c1 = load_fe<C>(p + 8);
 }
 template <class C>
 ZDEV void store_f(uint32_t* p, const Fe<C>& x) { store_fe(p, x); }
-ZDEV void store_f(uint32_t* p, const Fq2& x) {
+template <class C>
+ZDEV void store_f(uint32_t* p, const Fq2T<C>& x) {
   store_fe(p, x.c0);
   store_fe(p + 8, x.c1);
 }
@@ -303,8 +315,8 @@ template <class C>
 struct FWords<Fe<C>> {
   static constexpr int W = 8;
 };
-template <>
-struct FWords<Fq2> {
+template <class C>
+struct FWords<Fq2T<C>> {
   static constexpr int W = 16;
 };
 

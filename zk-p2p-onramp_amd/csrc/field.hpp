@@ -27,15 +27,52 @@ constexpr int NL = 9;
 constexpr int LB = 29;
 constexpr uint32_t LMASK = (1u << LB) - 1;
 
+// (a host tool that instantiates these templates on heavier types may define ZDEV without the forced inlining)
+#ifndef ZDEV
+#define ZDEV __host__ __device__ __forceinline__
+#endif
+
+// The limb and column-accumulator types of a field config, and what each primitive below reports about
+// its result.  Every real config computes on uint32_t limbs with a uint64_t column accumulator and
+// reports nothing: note() is empty and the op name it is given (ZFN: the name of the calling function,
+// "lsub8" for the borrow_sub inside lsub8) is dropped with it.  The bounds prover
+// (tools/hosttest/bounds.cpp) specialises FeTypes and Fe for configs whose limbs are integer intervals
+// and runs these same templates on them; its note() applies the value-level transfer function of the
+// primitive and checks its operand contract.  The few casts that depend on the limb type are spelled
+// as the functions wide / lo32 / sgn / unsg / select, which the prover overloads for its types.
+struct n_sop {};
+struct n_sqr {};
+struct n_shoup {};
+struct n_normalize {};
+struct n_cond_sub {};
+struct n_qreduce {};
+struct n_add_raw {};
+struct n_borrow_sub {};
+struct n_shl1 {};
+template <class C>
+struct FeTypes {
+  using limb = uint32_t;
+  using slimb = int32_t;
+  using acc = uint64_t;
+  template <class... A>
+  static ZDEV void note(const A&...) {}
+};
+#define ZFN const char* fn = __builtin_FUNCTION()
+
 template <class C>
 struct Fe {
-  uint32_t v[NL];
+  typename FeTypes<C>::limb v[NL];
 };
 
 using Fq = Fe<FqCfg>;
 using Fr = Fe<FrCfg>;
 
-#define ZDEV __host__ __device__ __forceinline__
+ZDEV uint64_t wide(uint32_t x) { return x; }             // limb -> accumulator
+ZDEV uint32_t lo32(uint64_t a) { return (uint32_t)a; }   // accumulator -> limb: truncates unless a < 2^32
+ZDEV int32_t sgn(uint32_t x) { return (int32_t)x; }      // limb read as a signed word
+ZDEV uint32_t unsg(int32_t x) { return (uint32_t)x; }
+template <class T>
+ZDEV T select(bool c, T a, T b) { return c ? a : b; }
 
 // acc += x * y.  CH (C::CHAIN, device code): every product column stays ONE dependent chain seeded
 // by the previous column's carry.  Left to itself the compiler re-associates each column into a sum
@@ -45,16 +82,16 @@ using Fr = Fe<FrCfg>;
 // instructions (it interleaves independent products' chains to cover the wait states between
 // dependent 64-bit mads).  tools/ubench/mul_chain.hip, profiles/mul_chain_r03.txt.  mac_k takes a
 // constant.  Host code is always plain C.
-template <bool CH>
-ZDEV void mac(uint64_t& acc, uint32_t x, uint32_t y) {
-  acc += (uint64_t)x * y;
+template <bool CH, class A, class T>
+ZDEV void mac(A& acc, T x, T y) {
+  acc += wide(x) * y;
 #if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (CH) asm("" : "+v"(acc));
 #endif
 }
-template <bool CH>
-ZDEV void mac_k(uint64_t& acc, uint32_t x, uint32_t k) {
-  acc += (uint64_t)x * k;
+template <bool CH, class A, class T>
+ZDEV void mac_k(A& acc, T x, uint32_t k) {
+  acc += wide(x) * k;
 #if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (CH) asm("" : "+v"(acc));
 #endif
@@ -92,15 +129,20 @@ ZDEV Fe<C> fe_one() { return fe_const<C>(C::ONE); }
 // with ONE reduction per lane ("lazy reduction": the N products' and the m MOD partial products of a
 // column accumulate together).  Column i takes a_j b_(i-j) for every j in range; m_i, the quotient
 // digit that clears the column, is fixed once the column's last product (j = i) is in.
-//   N = 1: a's limbs 0..7 < 2^30 (value < 8m; up to ~11m as long as a b < 169 m^2), or ONE operand
-//          with limbs < 2^31 against a normalised one (column sums < 9*2^60 + 9*2^58 + 2^35 < 2^64).
-//   N > 1: all operands normalised (limbs < 2^29; N = 4: columns hold <= 36 + 9 partial products
-//          < 2^58, < 2^63.5) and the sum < m 2^261 (~169 m^2).
+//   N = 1: both operands' limbs 0..7 < 2^30 (value < 8m; up to ~11m as long as a b < 169 m^2), or ONE
+//          operand with limbs < 2.5 * 2^30 (the largest raw form, sub_raw8) against a normalised one
+//          (column sums < 9 * 2.5 * 2^59 + 9 * 2^58 + 2^35 = 0.84 * 2^64).
+//   N = 2: all operands normalised but at most ONE, with limbs < 2^31 (the G1 Y3's d = rsub(0, PPP):
+//          columns < 9 * 2^60 + 18 * 2^58 + 2^35 = 0.84 * 2^64; two raw operands could reach 2^64).
+//   N = 4: all operands normalised (columns hold <= 36 + 9 partial products < 2^58, < 2^63.5).
+//   Every N: the sum < m 2^261 (~169 m^2).
 // Output: normalised limbs, value < 2m (sum / 2^261 + m).
+// These contracts, and every bound quoted in this file, are proven for all inputs by
+// tools/hosttest/bounds.cpp, which runs these templates on interval limbs.
 template <class C, bool CH, int L, int N>
-ZDEV void mont_sop(const Fe<C>* const (&a)[L][N], const Fe<C>* const (&b)[L][N], Fe<C>* const (&r)[L]) {
-  uint32_t m[L][NL];
-  uint64_t acc[L];
+ZDEV void mont_sop(const Fe<C>* const (&a)[L][N], const Fe<C>* const (&b)[L][N], Fe<C>* const (&r)[L], ZFN) {
+  typename FeTypes<C>::limb m[L][NL];
+  typename FeTypes<C>::acc acc[L];
   ZLANES acc[l] = 0;
 #pragma unroll
   for (int i = 0; i < 2 * NL - 1; ++i) {
@@ -108,23 +150,24 @@ ZDEV void mont_sop(const Fe<C>* const (&a)[L][N], const Fe<C>* const (&b)[L][N],
     for (int j = (i < NL ? 0 : i - NL + 1); j <= (i < NL ? i : NL - 1); ++j) {
 #pragma unroll
       for (int k = 0; k < N; ++k) ZLANES mac<CH>(acc[l], a[l][k]->v[j], b[l][k]->v[i - j]);
-      if (j == i) ZLANES m[l][i] = ((uint32_t)acc[l] * C::INV) & LMASK;
+      if (j == i) ZLANES m[l][i] = (lo32(acc[l]) * C::INV) & LMASK;
       ZLANES mac_k<CH>(acc[l], m[l][j], C::MOD[i - j]);
     }
-    if (i >= NL) ZLANES r[l]->v[i - NL] = (uint32_t)acc[l] & LMASK;
+    if (i >= NL) ZLANES r[l]->v[i - NL] = lo32(acc[l]) & LMASK;
     ZLANES acc[l] >>= LB;
   }
-  ZLANES r[l]->v[NL - 1] = (uint32_t)acc[l];
+  ZLANES r[l]->v[NL - 1] = lo32(acc[l]);
+  ZLANES FeTypes<C>::note(n_sop{}, fn, a[l], b[l], *r[l]);
 }
 
 // Montgomery squares r[l] = a[l]^2 / 2^261 mod m: cross products computed once against a doubled
 // operand.  Operand and output as mont_sop with N = 1 (a < 11m).
 template <class C, bool CH, int L>
-ZDEV void mont_sqr(const Fe<C>* const (&a)[L], Fe<C>* const (&r)[L]) {
-  uint32_t m[L][NL], d[L][NL];
+ZDEV void mont_sqr(const Fe<C>* const (&a)[L], Fe<C>* const (&r)[L], ZFN) {
+  typename FeTypes<C>::limb m[L][NL], d[L][NL];
 #pragma unroll
   for (int i = 0; i < NL; ++i) ZLANES d[l][i] = a[l]->v[i] << 1;
-  uint64_t acc[L];
+  typename FeTypes<C>::acc acc[L];
   ZLANES acc[l] = 0;
 #pragma unroll
   for (int i = 0; i < 2 * NL - 1; ++i) {
@@ -134,38 +177,39 @@ ZDEV void mont_sqr(const Fe<C>* const (&a)[L], Fe<C>* const (&r)[L]) {
     if ((i & 1) == 0) ZLANES mac<CH>(acc[l], a[l]->v[i / 2], a[l]->v[i / 2]);
 #pragma unroll
     for (int j = lo; j <= hi; ++j) {
-      if (j == i) ZLANES m[l][i] = ((uint32_t)acc[l] * C::INV) & LMASK;
+      if (j == i) ZLANES m[l][i] = (lo32(acc[l]) * C::INV) & LMASK;
       ZLANES mac_k<CH>(acc[l], m[l][j], C::MOD[i - j]);
     }
-    if (i >= NL) ZLANES r[l]->v[i - NL] = (uint32_t)acc[l] & LMASK;
+    if (i >= NL) ZLANES r[l]->v[i - NL] = lo32(acc[l]) & LMASK;
     ZLANES acc[l] >>= LB;
   }
-  ZLANES r[l]->v[NL - 1] = (uint32_t)acc[l];
+  ZLANES r[l]->v[NL - 1] = lo32(acc[l]);
+  ZLANES FeTypes<C>::note(n_sqr{}, fn, *a[l], *r[l]);
 }
 
 // Products by CONSTANTS with precomputed quotients (Shoup): r[l] = a[l] w[l] mod m for w < m given
 // as plain limbs and wq = floor(w 2^261 / m) (both normalised, 9 limbs).  q = floor(a wq / 2^261)
 // from the product columns 7..17 only (the dropped columns 0..6 sum to < 2^237, so q is the exact
 // floor or one less), then a w - q m = (a w + q (2^261 - m)) mod 2^261 from the low columns 0..8.
-// Since a w / m - a wq / 2^261 < a / 2^261 <= 1, the result is in [0, 3m).  a: limbs < 2^31 (a raw
-// sum or borrow-form difference is fine), value < 2^261.  A Montgomery-form a stays in Montgomery
+// Since a w / m - a wq / 2^261 < a / 2^261 <= 1, the result is in [0, 3m).  a: limbs < 2.5 * 2^30 (a raw
+// sum or borrow-form difference is fine: sub_raw8's is the largest), value < 2^261.  A Montgomery-form a stays in Montgomery
 // form (w is plain).  143 v_mad_u64_u32 and no per-column quotient digits, against 162 mads plus
 // 9 v_mul_lo_u32 for mul(); NTT roots, twiddles and the coset key are all constants.
 template <class C, int L>
 ZDEV void mont_shoup(const Fe<C>* const (&a)[L], const Fe<C>* const (&w)[L], const Fe<C>* const (&wq)[L],
-                     Fe<C>* const (&r)[L]) {
-  uint32_t q[L][NL];
-  uint64_t acc[L];
+                     Fe<C>* const (&r)[L], ZFN) {
+  typename FeTypes<C>::limb q[L][NL];
+  typename FeTypes<C>::acc acc[L];
   ZLANES acc[l] = 0;
 #pragma unroll
   for (int c = 7; c < 2 * NL - 1; ++c) {
 #pragma unroll
     for (int i = (c < NL ? 0 : c - NL + 1); i <= (c < NL ? c : NL - 1); ++i)
       ZLANES mac<C::CHAIN>(acc[l], a[l]->v[i], wq[l]->v[c - i]);
-    if (c >= NL) ZLANES q[l][c - NL] = (uint32_t)acc[l] & LMASK;
+    if (c >= NL) ZLANES q[l][c - NL] = lo32(acc[l]) & LMASK;
     ZLANES acc[l] >>= LB;
   }
-  ZLANES q[l][NL - 1] = (uint32_t)acc[l];  // columns 9..16 give q's limbs 0..7, the carry out its top limb (q < 2^261)
+  ZLANES q[l][NL - 1] = lo32(acc[l]);  // columns 9..16 give q's limbs 0..7, the carry out its top limb (q < 2^261)
   ZLANES acc[l] = 0;
 #pragma unroll
   for (int c = 0; c < NL; ++c) {
@@ -174,9 +218,10 @@ ZDEV void mont_shoup(const Fe<C>* const (&a)[L], const Fe<C>* const (&w)[L], con
       ZLANES mac<C::CHAIN>(acc[l], a[l]->v[i], w[l]->v[c - i]);
       ZLANES mac_k<C::CHAIN>(acc[l], q[l][i], C::NM[c - i]);
     }
-    ZLANES r[l]->v[c] = (uint32_t)acc[l] & LMASK;
+    ZLANES r[l]->v[c] = lo32(acc[l]) & LMASK;
     ZLANES acc[l] >>= LB;
   }
+  ZLANES FeTypes<C>::note(n_shoup{}, fn, *a[l], *w[l], *wq[l], *r[l]);
 }
 #undef ZLANES
 
@@ -264,35 +309,37 @@ ZDEV Fe<C> shoup_quot(const Fe<C>& wm) {
 
 // carry-propagate limbs 0..7 into 29-bit digits (limb values must be >= 0 and < 2^31)
 template <class C>
-ZDEV void normalize(Fe<C>& a) {
+ZDEV void normalize(Fe<C>& a, ZFN) {
 #pragma unroll
   for (int i = 0; i < NL - 1; ++i) {
     a.v[i + 1] += a.v[i] >> LB;
     a.v[i] &= LMASK;
   }
+  FeTypes<C>::note(n_normalize{}, fn, a);
 }
 template <class C>
-ZDEV Fe<C> normalized(Fe<C> s) {
-  normalize(s);
+ZDEV Fe<C> normalized(Fe<C> s, ZFN) {
+  normalize(s, fn);
   return s;
 }
 
-// a - M if a >= M else a   (a normalised; M normalised limbs)
+// a - M if a >= M else a   (a normalised, < 2^261; M normalised limbs)
 template <class C>
-ZDEV Fe<C> cond_sub(const Fe<C>& a, const uint32_t (&M)[NL]) {
+ZDEV Fe<C> cond_sub(const Fe<C>& a, const uint32_t (&M)[NL], ZFN) {
   Fe<C> d;
-  int32_t carry = 0;
+  typename FeTypes<C>::slimb carry = 0;
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
-    int32_t t = (int32_t)a.v[i] - (int32_t)M[i] + carry;
-    d.v[i] = (uint32_t)t & LMASK;
+    const auto t = sgn(a.v[i]) - (int32_t)M[i] + carry;
+    d.v[i] = unsg(t) & LMASK;
     carry = t >> LB;
   }
-  // top limb: keep full (non-masked) value when no borrow
-  const bool ge = carry >= 0;
+  // no borrow out of the top limb: a >= M, and the masked top limb of d is its whole value
+  const auto ge = carry >= 0;
   Fe<C> r;
 #pragma unroll
-  for (int i = 0; i < NL; ++i) r.v[i] = ge ? d.v[i] : a.v[i];
+  for (int i = 0; i < NL; ++i) r.v[i] = select(ge, d.v[i], a.v[i]);
+  FeTypes<C>::note(n_cond_sub{}, fn, a, M, r);
   return r;
 }
 
@@ -303,19 +350,22 @@ ZDEV Fe<C> cond_sub(const Fe<C>& a, const uint32_t (&M)[NL]) {
 // mod 2^261: per limb one v_mad_u64_u32 (q * NM[i] + s[i] + carry < 2^39), a mask and a shift,
 // instead of a carry pass plus one or two borrow-chain conditional subtractions with selects
 // (34 vs 65-105 instructions).  A top limb that went "negative" (uint32 wrap of a wide-borrow
-// form whose true top, after the lower carries, is >= 0) has a value < 2^235 < m: q = 0.
+// form whose true top, after the lower carries, is >= 0) has a value below the low limbs' own weight,
+// < 2^32 * 2^203 = 2^235 < m: q = 0, and the carry pass brings the top limb back because v >= 0.
 template <class C>
-ZDEV Fe<C> qreduce(const Fe<C>& s) {
-  const int32_t top = (int32_t)s.v[NL - 1];
-  const uint32_t q = top > 0 ? (uint32_t)(((uint64_t)(uint32_t)top * C::QK) >> 32) : 0u;
+ZDEV Fe<C> qreduce(const Fe<C>& s, ZFN) {
+  using limb = typename FeTypes<C>::limb;
+  const auto top = sgn(s.v[NL - 1]);
+  const limb q = top > 0 ? limb(lo32((wide(unsg(top)) * C::QK) >> 32)) : limb(0u);
   Fe<C> r;
-  uint32_t carry = 0;
+  limb carry = 0;
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
-    const uint64_t acc = (uint64_t)q * C::NM[i] + (uint64_t)(s.v[i] + carry);
-    r.v[i] = (uint32_t)acc & LMASK;
-    carry = (uint32_t)(acc >> LB);
+    const auto acc = wide(q) * C::NM[i] + wide(s.v[i] + carry);
+    r.v[i] = lo32(acc) & LMASK;
+    carry = lo32(acc >> LB);
   }
+  FeTypes<C>::note(n_qreduce{}, fn, s, r);
   return r;
 }
 
@@ -323,36 +373,37 @@ ZDEV Fe<C> qreduce(const Fe<C>& s) {
 // per transform), carry pass + one conditional subtraction for Fq, whose XYZZ kernels are
 // register-bound (qreduce's 64-bit temporaries: 124 -> 135 VGPRs in k_accumulate, 4 -> 3 waves).
 template <class C>
-ZDEV Fe<C> reduce2(Fe<C> s) {
+ZDEV Fe<C> reduce2(Fe<C> s, ZFN) {
   if constexpr (C::QRED) {
-    return qreduce(s);
+    return qreduce(s, fn);
   } else {
-    normalize(s);
-    return cond_sub(s, C::MOD2);
+    normalize(s, fn);
+    return cond_sub(s, C::MOD2, fn);
   }
 }
 
 // x < 8m (normalised) -> < 2m
 template <class C>
-ZDEV Fe<C> canon8(const Fe<C>& a) { return cond_sub(cond_sub(a, C::MOD4), C::MOD2); }
+ZDEV Fe<C> canon8(const Fe<C>& a, ZFN) { return cond_sub(cond_sub(a, C::MOD4, fn), C::MOD2, fn); }
 
 // s (limbs 0..7 >= 0 and < 2^32 - 2^10, Fq: < 2^31; value in [0, 8m)) -> < 2m (Fr: qreduce, < 1.2m)
 template <class C>
-ZDEV Fe<C> reduce8(Fe<C> s) {
+ZDEV Fe<C> reduce8(Fe<C> s, ZFN) {
   if constexpr (C::QRED) {
-    return qreduce(s);
+    return qreduce(s, fn);
   } else {
-    normalize(s);
-    return canon8(s);
+    normalize(s, fn);
+    return canon8(s, fn);
   }
 }
 
 // a + b limb by limb, raw: no carry pass, no reduction
 template <class C>
-ZDEV Fe<C> add_raw(const Fe<C>& a, const Fe<C>& b) {
+ZDEV Fe<C> add_raw(const Fe<C>& a, const Fe<C>& b, ZFN) {
   Fe<C> s;
 #pragma unroll
   for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] + b.v[i];
+  FeTypes<C>::note(n_add_raw{}, fn, a, b, s);
   return s;
 }
 
@@ -364,13 +415,14 @@ ZDEV Fe<C> add_raw(const Fe<C>& a, const Fe<C>& b) {
 // directly; a table bound to a reference stays in memory and its limbs arrive by scalar loads.
 #define ZTAB(K) [](int i) { return C::K[i]; }
 template <class C, class T>
-ZDEV Fe<C> borrow_sub(const Fe<C>& a, T K, const Fe<C>& b, const Fe<C>* c = nullptr) {
+ZDEV Fe<C> borrow_sub(const Fe<C>& a, T K, const Fe<C>& b, const Fe<C>* c = nullptr, ZFN) {
   Fe<C> s;
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
     s.v[i] = a.v[i] + K(i) - b.v[i];
     if (c) s.v[i] -= c->v[i] << 1;
   }
+  FeTypes<C>::note(n_borrow_sub{}, fn, a, K, b, c, s);
   return s;
 }
 
@@ -397,8 +449,9 @@ ZDEV Fe<C> sub4(const Fe<C>& a, const Fe<C>& b) { return reduce8(borrow_sub(a, Z
 template <class C>
 ZDEV Fe<C> lsub(const Fe<C>& a, const Fe<C>& b) { return normalized(borrow_sub(a, ZTAB(MOD2_BORROW), b)); }
 
-// a - b + 4m, NOT normalised (every limb in [0, 2^31), value < 6m): ONE operand of
-// mul() whose other operand is normalised; never sqr(), add(), sub(), is_zero(), storage
+// a - b + 4m for a, b < 2m, NOT normalised (every limb in [0, 2^31), value < 6m; b < 3m as in the NTT:
+// limbs < 1.5 * 2^30, value < 7m for a < 3m): ONE operand of mul() / mul2() whose other operands are
+// normalised, or of mul_shoup() / qreduce(); never sqr(), add(), sub(), is_zero(), storage
 template <class C>
 ZDEV Fe<C> rsub(const Fe<C>& a, const Fe<C>& b) { return borrow_sub(a, ZTAB(MOD4_BORROW), b); }
 
@@ -434,10 +487,11 @@ ZDEV Fe<C> lsub6(const Fe<C>& a, const Fe<C>& b) { return normalized(borrow_sub(
 
 // 2a, limbs shifted (raw: limbs < 2^30 for a normalised a): ONE operand of mul()
 template <class C>
-ZDEV Fe<C> shl1_raw(const Fe<C>& a) {
+ZDEV Fe<C> shl1_raw(const Fe<C>& a, ZFN) {
   Fe<C> s;
 #pragma unroll
   for (int i = 0; i < NL; ++i) s.v[i] = a.v[i] << 1;
+  FeTypes<C>::note(n_shl1{}, fn, a, s);
   return s;
 }
 
@@ -477,7 +531,7 @@ ZDEV Fe<C> canon(const Fe<C>& a) { return cond_sub(a, C::MOD); }
 
 template <class C>
 ZDEV bool is_zero_raw(const Fe<C>& a) {
-  uint32_t o = 0;
+  typename FeTypes<C>::limb o = 0;
 #pragma unroll
   for (int i = 0; i < NL; ++i) o |= a.v[i];
   return o == 0;
@@ -486,7 +540,7 @@ ZDEV bool is_zero_raw(const Fe<C>& a) {
 // value (< 2m) congruent to 0 mod m
 template <class C>
 ZDEV bool is_zero(const Fe<C>& a) {
-  uint32_t o = 0, q = 0;
+  typename FeTypes<C>::limb o = 0, q = 0;
 #pragma unroll
   for (int i = 0; i < NL; ++i) {
     o |= a.v[i];
@@ -573,13 +627,16 @@ ZDEV Fe<C> inv(const Fe<C>& a) {
 
 // ---------------------------------------------------------------- Fq2 = Fq[u]/(u^2+1)
 
-struct Fq2 {
-  Fq c0, c1;
+// Written for any config of the base field (the kernels use Fq2 = Fq2T<FqCfg> only).
+template <class C>
+struct Fq2T {
+  Fe<C> c0, c1;
 };
+using Fq2 = Fq2T<FqCfg>;
 
-// 4m - a, normalised, for a normalised a <= 4m (Fq2 components are < 4m: rsub's)
-ZDEV Fq neg4(const Fq& a) {
-  using C = FqCfg;
+// 4m - a, normalised, for a normalised a <= 4m (Fq2 components are < 4m: rsub's); result <= 4m
+template <class C>
+ZDEV Fe<C> neg4(const Fe<C>& a) {
   return normalized(borrow_sub(fe_zero<C>(), ZTAB(MOD4_BORROW), a));
 }
 
@@ -588,27 +645,30 @@ ZDEV Fq neg4(const Fq& a) {
 // subtractions: ~650 instead of ~1100 instructions).  Components normalised, < 4m.
 // The two components' sums of products are the two lanes of one mont_sop with chained columns: the
 // 2-wave G2 kernels gain with paired chains (profiles/g2_chain_r03.txt).
-ZDEV Fq2 mul(const Fq2& a, const Fq2& b) {
-  Fq2 r;
-  const Fq nb1 = neg4(b.c1);
-  mont_sop<FqCfg, true, 2, 2>({{&a.c0, &a.c1}, {&a.c0, &a.c1}}, {{&b.c0, &nb1}, {&b.c1, &b.c0}}, {&r.c0, &r.c1});
+template <class C>
+ZDEV Fq2T<C> mul(const Fq2T<C>& a, const Fq2T<C>& b) {
+  Fq2T<C> r;
+  const Fe<C> nb1 = neg4(b.c1);
+  mont_sop<C, true, 2, 2>({{&a.c0, &a.c1}, {&a.c0, &a.c1}}, {{&b.c0, &nb1}, {&b.c1, &b.c0}}, {&r.c0, &r.c1});
   return r;
 }
 
 // a*b + c*d in Fq2 with two lazily reduced four-product sums
-ZDEV Fq2 mul2(const Fq2& a, const Fq2& b, const Fq2& c, const Fq2& d) {
-  Fq2 r;
-  const Fq nb1 = neg4(b.c1), nd1 = neg4(d.c1);
-  mont_sop<FqCfg, true, 2, 4>({{&a.c0, &a.c1, &c.c0, &c.c1}, {&a.c0, &a.c1, &c.c0, &c.c1}},
-                              {{&b.c0, &nb1, &d.c0, &nd1}, {&b.c1, &b.c0, &d.c1, &d.c0}}, {&r.c0, &r.c1});
+template <class C>
+ZDEV Fq2T<C> mul2(const Fq2T<C>& a, const Fq2T<C>& b, const Fq2T<C>& c, const Fq2T<C>& d) {
+  Fq2T<C> r;
+  const Fe<C> nb1 = neg4(b.c1), nd1 = neg4(d.c1);
+  mont_sop<C, true, 2, 4>({{&a.c0, &a.c1, &c.c0, &c.c1}, {&a.c0, &a.c1, &c.c0, &c.c1}},
+                          {{&b.c0, &nb1, &d.c0, &nd1}, {&b.c1, &b.c0, &d.c1, &d.c0}}, {&r.c0, &r.c1});
   return r;
 }
 
-ZDEV Fq2 sqr(const Fq2& a) {
+template <class C>
+ZDEV Fq2T<C> sqr(const Fq2T<C>& a) {
   // (a0 + a1 u)^2 = (a0+a1)(a0-a1) + 2 a0 a1 u
-  Fq2 r;
+  Fq2T<C> r;
   r.c0 = mul(add(a.c0, a.c1), sub(a.c0, a.c1));
-  Fq t = mul(a.c0, a.c1);
+  Fe<C> t = mul(a.c0, a.c1);
   r.c1 = add(t, t);
   return r;
 }
@@ -617,45 +677,59 @@ ZDEV Fq2 sqr(const Fq2& a) {
 // bounds as noted; the products stay < 2m as long as each Fq sum of products of a Fq2 mul/mul2
 // (neg4 on the second operand's c1, which must be <= 4m) stays below ~169 m^2.
 // a - b + 2m per component for a, b < 2m: < 4m, no conditional subtraction
-ZDEV Fq2 lsub2_lazy(const Fq2& a, const Fq2& b) { return Fq2{lsub(a.c0, b.c0), lsub(a.c1, b.c1)}; }
+template <class C>
+ZDEV Fq2T<C> lsub2_lazy(const Fq2T<C>& a, const Fq2T<C>& b) { return Fq2T<C>{lsub(a.c0, b.c0), lsub(a.c1, b.c1)}; }
 // a - b + 4m per component for a < 2m, b < 4m: < 6m
-ZDEV Fq2 lsub4_lazy(const Fq2& a, const Fq2& b) { return Fq2{lsub4(a.c0, b.c0), lsub4(a.c1, b.c1)}; }
+template <class C>
+ZDEV Fq2T<C> lsub4_lazy(const Fq2T<C>& a, const Fq2T<C>& b) { return Fq2T<C>{lsub4(a.c0, b.c0), lsub4(a.c1, b.c1)}; }
 // a^2 for components < 6m: (a0 + a1)(a0 - a1 + 6m) [raw sum x normalised, < 144 m^2] and
 // (2 a0) a1 [raw x normalised, < 72 m^2] -- no additions reduced, no doubling of the product
-ZDEV Fq2 sqr_lazy(const Fq2& a) {
-  const Fq s = add_raw(a.c0, a.c1), d = lsub6(a.c0, a.c1), t = shl1_raw(a.c0);
-  Fq2 r;
-  mont_sop<FqCfg, true, 2, 1>({{&s}, {&t}}, {{&d}, {&a.c1}}, {&r.c0, &r.c1});
+template <class C>
+ZDEV Fq2T<C> sqr_lazy(const Fq2T<C>& a) {
+  const Fe<C> s = add_raw(a.c0, a.c1), d = lsub6(a.c0, a.c1), t = shl1_raw(a.c0);
+  Fq2T<C> r;
+  mont_sop<C, true, 2, 1>({{&s}, {&t}}, {{&d}, {&a.c1}}, {&r.c0, &r.c1});
   return r;
 }
 // R^2 - PPP - 2Q per component (each < 2m) -> < 4m: one conditional subtraction instead of two.
 // (Not qreduce: its single 27-deep dependent chain per component measured 6 % slower in the
 // G2 accumulation, which runs at two waves per SIMD and cannot hide the latency.)
-ZDEV Fq2 sub_2x4(const Fq2& a, const Fq2& b, const Fq2& c) {
-  return Fq2{cond_sub(sub_2x8(a.c0, b.c0, c.c0), FqCfg::MOD4), cond_sub(sub_2x8(a.c1, b.c1, c.c1), FqCfg::MOD4)};
+template <class C>
+ZDEV Fq2T<C> sub_2x4(const Fq2T<C>& a, const Fq2T<C>& b, const Fq2T<C>& c) {
+  return Fq2T<C>{cond_sub(sub_2x8(a.c0, b.c0, c.c0), C::MOD4), cond_sub(sub_2x8(a.c1, b.c1, c.c1), C::MOD4)};
 }
 // components < 4m -> < 2m
-ZDEV Fq2 canon4(const Fq2& a) { return Fq2{cond_sub(a.c0, FqCfg::MOD2), cond_sub(a.c1, FqCfg::MOD2)}; }
+template <class C>
+ZDEV Fq2T<C> canon4(const Fq2T<C>& a) { return Fq2T<C>{cond_sub(a.c0, C::MOD2), cond_sub(a.c1, C::MOD2)}; }
 
-ZDEV Fq2 add(const Fq2& a, const Fq2& b) { return Fq2{add(a.c0, b.c0), add(a.c1, b.c1)}; }
+template <class C>
+ZDEV Fq2T<C> add(const Fq2T<C>& a, const Fq2T<C>& b) { return Fq2T<C>{add(a.c0, b.c0), add(a.c1, b.c1)}; }
 // The generic (non-accumulator) lazy names on Fq2, as the doubling formulas of curve.hpp use them.
 // An Fq2 mul() / mul2() is a sum of several products per component, so EVERY operand must be
 // normalised (no raw operand as in the one-product Fq mul), and neg4 wants the second operand's c1
 // <= 4m: rsub is therefore the normalised lsub per component (< 4m).  sqr() reduces its operand's
 // components with add() / sub(), which take values < 2m: lsub is the fully reduced sub.
-ZDEV Fq2 sub_2x(const Fq2& a, const Fq2& b, const Fq2& c) {
-  return Fq2{sub_2x(a.c0, b.c0, c.c0), sub_2x(a.c1, b.c1, c.c1)};
+template <class C>
+ZDEV Fq2T<C> sub_2x(const Fq2T<C>& a, const Fq2T<C>& b, const Fq2T<C>& c) {
+  return Fq2T<C>{sub_2x(a.c0, b.c0, c.c0), sub_2x(a.c1, b.c1, c.c1)};
 }
-ZDEV Fq2 lsub(const Fq2& a, const Fq2& b) { return Fq2{sub(a.c0, b.c0), sub(a.c1, b.c1)}; }
-ZDEV Fq2 rsub(const Fq2& a, const Fq2& b) { return Fq2{lsub(a.c0, b.c0), lsub(a.c1, b.c1)}; }
-ZDEV Fq2 sub(const Fq2& a, const Fq2& b) { return Fq2{sub(a.c0, b.c0), sub(a.c1, b.c1)}; }
-ZDEV Fq2 dbl(const Fq2& a) { return add(a, a); }
-ZDEV bool is_zero(const Fq2& a) { return is_zero(a.c0) && is_zero(a.c1); }
-ZDEV bool is_zero_raw(const Fq2& a) { return is_zero_raw(a.c0) && is_zero_raw(a.c1); }
+template <class C>
+ZDEV Fq2T<C> lsub(const Fq2T<C>& a, const Fq2T<C>& b) { return Fq2T<C>{sub(a.c0, b.c0), sub(a.c1, b.c1)}; }
+template <class C>
+ZDEV Fq2T<C> rsub(const Fq2T<C>& a, const Fq2T<C>& b) { return Fq2T<C>{lsub(a.c0, b.c0), lsub(a.c1, b.c1)}; }
+template <class C>
+ZDEV Fq2T<C> sub(const Fq2T<C>& a, const Fq2T<C>& b) { return Fq2T<C>{sub(a.c0, b.c0), sub(a.c1, b.c1)}; }
+template <class C>
+ZDEV Fq2T<C> dbl(const Fq2T<C>& a) { return add(a, a); }
+template <class C>
+ZDEV bool is_zero(const Fq2T<C>& a) { return is_zero(a.c0) && is_zero(a.c1); }
+template <class C>
+ZDEV bool is_zero_raw(const Fq2T<C>& a) { return is_zero_raw(a.c0) && is_zero_raw(a.c1); }
 // (c0 + c1 u)^-1 = (c0 - c1 u) / (c0^2 + c1^2)
-ZDEV Fq2 inv(const Fq2& a) {
-  const Fq t = inv(add(sqr(a.c0), sqr(a.c1)));
-  return Fq2{mul(a.c0, t), mul(sub(fe_zero<FqCfg>(), a.c1), t)};
+template <class C>
+ZDEV Fq2T<C> inv(const Fq2T<C>& a) {
+  const Fe<C> t = inv(add(sqr(a.c0), sqr(a.c1)));
+  return Fq2T<C>{mul(a.c0, t), mul(sub(fe_zero<C>(), a.c1), t)};
 }
 
 }  // namespace zkp

@@ -6,6 +6,7 @@
 #include "field.hpp"
 #include "hip_check.hpp"
 #include "host_ec.hpp"
+#include "ntt_unit.hpp"
 
 namespace zkp {
 
@@ -108,8 +109,6 @@ __device__ __forceinline__ void lds_put(uint32_t* __restrict__ lds, int E_rt, in
 #pragma unroll
   for (int l = 0; l < NL; ++l) lds[l * E + e] = x.v[l];
 }
-// x - y for stage values (Shoup products: < 3m)
-__device__ __forceinline__ Fr stage_sub(const Fr& x, const Fr& y) { return sub4(x, y); }
 // a * w_ja and c * w_jc as one lockstep pair of Shoup products (field.hpp mul_shoup_pair; with Fr's
 // chained columns the two chains fill each other's wait states); outputs < 3m
 __device__ __forceinline__ void root_mul_pair(const Fr& a, uint32_t ja, const Fr& c, uint32_t jc,
@@ -137,14 +136,11 @@ __device__ __forceinline__ Fr root_mul(const Fr& a, uint32_t j, const uint32_t* 
 
 // one radix-4 unit (thread work item q) of round t: rows r0 + {0, H/2, H, 3H/2} of stage t
 // (span H) and t+1 (span H/2), r0 = grp 2H + i.
-// Value bounds (round 5, host-tested: tools/hosttest op r4lazy): every tile value between rounds is
-// normalised (limbs < 2^29) and < 3m (Shoup outputs < 3m, qreduce outputs < 1.2m).  The first-stage
-// sums stay raw (< 6m, limbs < 2^30); their difference takes the 2^30-raised 8m borrow form without a
-// carry pass (sub_raw8: limbs < 2.5 * 2^30, < 6m + 8m = 14m), a mul_shoup operand.  RAW: the unit is the
-// last one of a DFT whose outputs only feed a Montgomery product (the DIF pass's inter-pass twiddle, the
-// coset key between the fused kernel's two DFTs): its four outputs stay unreduced (< 14m, limbs
-// < 2.5 * 2^30 -- a mul() operand against the normalised table value < 2m: 28 m^2, far below the
-// 169 m^2 that keeps a product < 2m, field.hpp mont_sop), 4 reductions fewer.
+// The arithmetic and its value bounds: ntt_unit.hpp ZKP_NTT_R4, expanded here over the LDS root table
+// and the unit's four rows.
+#define ZRMP(a, ja, c, jc, r, s) root_mul_pair(a, ja, c, jc, ltw, r, s)
+#define ZRM1(a, j) root_mul(a, j, ltw)
+#define ZPUT(k, y) lds_put<LE>(lds, E, p##k, y)
 template <int LE>
 __device__ __forceinline__ void r4_unit(uint32_t* __restrict__ lds, const uint32_t* __restrict__ ltw, int E, int b,
                                         int lc, int t, int q, bool raw) {
@@ -161,40 +157,7 @@ __device__ __forceinline__ void r4_unit(uint32_t* __restrict__ lds, const uint32
   const int p0 = swz(base + (int)(r0 << lc)), p1 = p0 ^ swz(st), p2 = p0 ^ swz(2 * st), p3 = p0 ^ swz(3 * st);
   const Fr x0 = lds_get<LE>(lds, E, p0), x1 = lds_get<LE>(lds, E, p1), x2 = lds_get<LE>(lds, E, p2),
            x3 = lds_get<LE>(lds, E, p3);
-  // stage t: (x0, x2) with w_(2H)^i, (x1, x3) with w_(2H)^(i + H/2); stage t+1: (s02, s13)
-  // and (d02, d13), both with w_H^i.  Roots as exponents of w_(2^b) (stage t: i << t).
-  // the unit's independent root products in lockstep pairs (d02 / d13, then y1 / y3 by the same
-  // root); inside a round every lane multiplies (w^0 = 1 for i = 0: no divergent j == 0 path).  The
-  // last pair of a DFT (Hh == 1, a round-uniform branch; odd b too, dft_stages) has i = 0 for every lane: stage t's
-  // first difference takes w^0 = 1 and is only reduced (qreduce: < 1.2m, ~43 instructions instead of
-  // half a lockstep Shoup pair)
-  const uint32_t j = i << (t + 1);
-  Fr d02, d13;
-  if (Hh > 1) {
-    root_mul_pair(rsub(x0, x2), i << t, rsub(x1, x3), (i + Hh) << t, ltw, d02, d13);
-  } else {
-    d02 = qreduce(rsub(x0, x2));
-    d13 = root_mul(rsub(x1, x3), 1u << t, ltw);
-  }
-  const Fr s02 = add_raw(x0, x2), s13 = add_raw(x1, x3);  // < 6m, limbs < 2^30
-  if (Hh > 1) {
-    lds_put<LE>(lds, E, p0, add_raw_reduce(s02, s13));
-    Fr y1, y3;
-    root_mul_pair(sub_raw8(s02, s13), j, rsub(d02, d13), j, ltw, y1, y3);
-    lds_put<LE>(lds, E, p1, y1);
-    lds_put<LE>(lds, E, p3, y3);
-    lds_put<LE>(lds, E, p2, add(d02, d13));
-  } else if (raw) {  // last pair (span 1, no multiply in stage t+1), outputs into a Montgomery product
-    lds_put<LE>(lds, E, p0, add_raw(s02, s13));    // < 12m, limbs < 2^31
-    lds_put<LE>(lds, E, p1, sub_raw8(s02, s13));   // < 14m, limbs < 2.5 * 2^30
-    lds_put<LE>(lds, E, p2, add_raw(d02, d13));    // < 6m, limbs < 2^30
-    lds_put<LE>(lds, E, p3, rsub(d02, d13));       // < 7m, limbs < 1.5 * 2^30
-  } else {  // last pair, outputs stored: one reduction each
-    lds_put<LE>(lds, E, p0, add_raw_reduce(s02, s13));
-    lds_put<LE>(lds, E, p1, qreduce(sub_raw8(s02, s13)));
-    lds_put<LE>(lds, E, p2, add(d02, d13));
-    lds_put<LE>(lds, E, p3, stage_sub(d02, d13));
-  }
+  ZKP_NTT_R4(Fr, ZRMP, ZRM1, ZPUT)
 }
 
 // b radix-2 DIF stages on the LDS tile (rows natural in, bit-reversed out), done two at a
@@ -222,20 +185,14 @@ __device__ __forceinline__ void dft_stages(uint32_t* __restrict__ lds, const uin
     };
     for (int q = threadIdx.x; q < (E >> 1); q += 2 * NTT_TPB) {
       uint32_t ra, rc;
-      const int a0 = pos(q, ra), a1 = a0 ^ stp;
-      const Fr x0 = lds_get<LE>(lds, E, a0), x1 = lds_get<LE>(lds, E, a1);
+      const int p0 = pos(q, ra), p1 = p0 ^ stp;
+      const Fr x0 = lds_get<LE>(lds, E, p0), x1 = lds_get<LE>(lds, E, p1);
       if (q + NTT_TPB < (E >> 1)) {
-        const int c0 = pos(q + NTT_TPB, rc), c1 = c0 ^ stp;
-        const Fr y0 = lds_get<LE>(lds, E, c0), y1 = lds_get<LE>(lds, E, c1);
-        Fr u, v;
-        root_mul_pair(rsub(x0, x1), ra, rsub(y0, y1), rc, ltw, u, v);
-        lds_put<LE>(lds, E, a0, add(x0, x1));
-        lds_put<LE>(lds, E, a1, u);
-        lds_put<LE>(lds, E, c0, add(y0, y1));
-        lds_put<LE>(lds, E, c1, v);
+        const int p2 = pos(q + NTT_TPB, rc), p3 = p2 ^ stp;
+        const Fr y0 = lds_get<LE>(lds, E, p2), y1 = lds_get<LE>(lds, E, p3);
+        ZKP_NTT_R2_FIRST_PAIR(Fr, ZRMP, ZPUT)
       } else {
-        lds_put<LE>(lds, E, a1, root_mul(rsub(x0, x1), ra, ltw));
-        lds_put<LE>(lds, E, a0, add(x0, x1));
+        ZKP_NTT_R2_FIRST_ONE(ZRM1, ZPUT)
       }
     }
     __syncthreads();
@@ -251,13 +208,7 @@ __device__ __forceinline__ void dft_stages(uint32_t* __restrict__ lds, const uin
       const uint32_t bl = (uint32_t)q >> (lc + b - 1);
       const int p0 = swz((int)(bl << (b + lc)) + (int)((bq << 1) << lc) + (int)col), p1 = p0 ^ swz((int)C);
       const Fr x = lds_get<LE>(lds, E, p0), y = lds_get<LE>(lds, E, p1);
-      if (raw) {  // < 6m and < 7m, into a Montgomery product
-        lds_put<LE>(lds, E, p0, add_raw(x, y));
-        lds_put<LE>(lds, E, p1, rsub(x, y));
-      } else {
-        lds_put<LE>(lds, E, p0, add(x, y));
-        lds_put<LE>(lds, E, p1, stage_sub(x, y));  // span 1: the root is w_2^0 = 1
-      }
+      ZKP_NTT_R2_LAST(ZPUT)
     }
     __syncthreads();
   }
