@@ -38,7 +38,10 @@ def main(trace_csv, marker_csv, bench_json, out=None):
     peak = line["roofline"]["peak"]
     t0, t1 = timed_range(marker_csv)
     h_wg = set(per_kind["H"]["workgroups"])
-    w_wg = set(per_kind["A"]["workgroups"]) if "A" in per_kind else set()
+    # the witness launches: one grid per kind since each takes its own table's plan (A, B1, C may differ)
+    w_wg = set()
+    for k in ("A", "B1", "C"):
+        w_wg |= set(per_kind[k]["workgroups"]) if k in per_kind else set()
     if h_wg & w_wg:
         raise SystemExit("H and witness launches share a grid size %s: cannot split by grid" % (h_wg & w_wg))
     disp = []

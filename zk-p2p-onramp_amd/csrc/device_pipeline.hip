@@ -116,6 +116,11 @@ MsmOptions msm_options() {
       o.wsel = val == "first" ? 1 : (val == "second" ? 2 : 0);
       continue;
     }
+    if (key == "sparse") {
+      if (val != "0" && val != "1") throw ZkpError(ZKP_ERR_INVALID_ARG, "ZKP_MSM: sparse=0|1");
+      o.sparse = val == "1" ? 1 : 0;
+      continue;
+    }
     char* stop = nullptr;
     const long v = std::strtol(val.c_str(), &stop, 10);
     if (val.empty() || *stop || v <= 0 || v > (1 << 20))
@@ -233,6 +238,7 @@ DevicePipeline::DevicePipeline(int dev, const ZkeyParsed& z, int part, int npart
   MsmParams pw, ph;
   choose_msm_params(nv, nd, opt, pw, ph);
   wsel_opt_ = opt.wsel;
+  sparse_ = opt.sparse != 0;
   // base tables: A, B1, C, B2 indexed by witness signal (C's first nPublic+1 bases are
   // infinity, so one witness plan serves all four), H by domain index
   auto build_wtables = [&](WSet& w) {
@@ -247,6 +253,7 @@ DevicePipeline::DevicePipeline(int dev, const ZkeyParsed& z, int part, int npart
     const size_t lead = std::min(cfirst, whi_) - wlo_;
     const size_t cnt = whi_ > cfirst ? whi_ - cfirst : 0;
     fill_bases(*w.tc, cnt ? z.bf.sec[8].ptr + (cfirst - c0) * 64 : nullptr, cnt, lead, s0_);
+    w.mb = std::make_shared<BaseMask>(mask_union(*w.tb1, *w.tb2, s0_));
   };
   if (share) {
     if (share->dev_ != dev_ || share->wlo_ != wlo_ || share->whi_ != whi_ || share->hlo_ != hlo_ ||
@@ -256,6 +263,7 @@ DevicePipeline::DevicePipeline(int dev, const ZkeyParsed& z, int part, int npart
     for (int k = 0; k < nws_; ++k) {
       const WSet& o = share->ws_[k];
       ws_[k].pw = o.pw, ws_[k].ta = o.ta, ws_[k].tb1 = o.tb1, ws_[k].tc = o.tc, ws_[k].tb2 = o.tb2;
+      ws_[k].mb = o.mb;
     }
     th_ = share->th_;
     // the H plan and engine must read th_ with the parameters it was built with: a sibling's own
@@ -301,7 +309,8 @@ DevicePipeline::DevicePipeline(int dev, const ZkeyParsed& z, int part, int npart
   // witness upload slots: each has its own copy stream, so a proof's
   // witness H2D runs outside the compute lock and overlaps the proof in flight, and its own pinned
   // staging buffer and copy threads (upload()); allocated on the slot's first host-witness upload
-  // (ensure_upload_slot), so staged-only and split provers hold no pinned staging or copy threads
+  // (ensure_upload_slot) except slot 0 of a device's first full pipeline (below), so split provers and
+  // staged-only sibling pipelines hold no pinned staging or copy threads
   for (auto& b : abc_) b = DevBuf<>(nd_all * 8);
   pscal_ = DevBuf<>(nd_all * 8);
   ntt_ = std::make_unique<NttEngine>((int)h.log_domain, s0_);
@@ -332,9 +341,38 @@ DevicePipeline::DevicePipeline(int dev, const ZkeyParsed& z, int part, int npart
   hwin_ = PinnedBuf<uint32_t>(win_total());
   // a full prover's first upload slot exists from load on, so a one-shot prover's first host-witness
   // proof does not pay its ~410 MB of HBM, ~220 MB of pinned memory, streams and copy threads, and an
-  // out-of-memory surfaces here rather than at prove time; the second slot stays lazy
-  if (nparts == 1) ensure_upload_slot(0);
+  // out-of-memory surfaces here rather than at prove time; the second slot stays lazy, and
+  // so does every slot of a pipeline that shares another one's tables (ZKP_INFLIGHT siblings, the
+  // repeated ordinals of a rehearsal: their HBM goes to the second witness configuration first)
+  if (nparts == 1 && !share) ensure_upload_slot(0);
   HIPX(hipStreamSynchronize(s0_));
+}
+
+void DevicePipeline::build_engines(WSet& w) {
+  const bool sp = sparse_;
+  w.mask[PL_B] = sp ? w.mb->list() : nullptr;
+  w.mask[PL_A] = sp ? w.ta->present_index() : nullptr;
+  w.mask[PL_C] = sp ? w.tc->present_index() : nullptr;
+  w.present[PL_B] = w.mask[PL_B] ? w.mb->count : nv_;
+  w.present[PL_A] = w.mask[PL_A] ? w.ta->present_count() : nv_;
+  w.present[PL_C] = w.mask[PL_C] ? w.tc->present_count() : nv_;
+  // the sort's scratch (16 of a plan's ~20 bytes per entry) once, sized for the fullest plan; every
+  // plan's own outputs by its mask's count
+  auto scratch = std::make_shared<MsmSortScratch>(
+      nv_, std::max(w.present[PL_B], std::max(w.present[PL_A], w.present[PL_C])), w.pw);
+  for (int p = 0; p < NPLAN; ++p) {
+    w.plan[p] = nullptr;
+    for (int q = 0; q < p && !w.mask[p]; ++q)
+      if (!w.mask[q]) {
+        w.plan[p] = w.plan[q];
+        break;
+      }
+    if (w.plan[p]) continue;
+    w.own[p] = std::make_unique<MsmPlan>(nv_, w.pw, s3_, w.present[p], scratch);
+    w.plan[p] = w.own[p].get();
+  }
+  for (auto& g : w.g1) g = std::make_unique<MsmEngine>(Curve::G1, w.pw, nv_, s2_);
+  w.g2 = std::make_unique<MsmEngine>(Curve::G2, w.pw, nv_, s1_);
 }
 
 void DevicePipeline::add_second_wset() {
@@ -346,9 +384,7 @@ void DevicePipeline::add_second_wset() {
   } catch (const HipError& e) {
     if (e.code != hipErrorOutOfMemory) throw;
     (void)hipGetLastError();
-    ws_[1].plan.reset();
-    for (auto& g : ws_[1].g1) g.reset();
-    ws_[1].g2.reset();
+    ws_[1].drop_engines();
   }
 }
 
@@ -593,7 +629,8 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
   uint32_t* wa = dwin_;
   uint32_t* wh = dwin_ + 3 * wina_;
   uint32_t* wb2 = wh + winh_;
-  // s2: witness plan, then the G1 accumulations A, B1, C back to back; s3 finishes each
+  // s3: the witness plans B, A, C (one per mask of finite bases, each MSM takes its table's);
+  // s2: the G1 accumulations A, B1, C back to back; s3 finishes each
   // (merges + reduction: latency-bound chains) while s2 accumulates the next;
   // s1: G2 MSM B2 on the same plan; s0: quotient (buildABC, 3 coset NTTs, joinABC),
   // H plan, H MSM.  A starts when the G2 accumulation ends: the G2 finish (a latency-bound chain
@@ -602,7 +639,8 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
   // profiles/g2_first_ab_r06.txt).
   // MsmPlan::build blocks its host thread once (the sort needs the nonzero-digit
   // count), so each stream is fed from its own host thread; the G2 thread starts
-  // once the witness plan is enqueued (its stream then waits on plan.ready()).
+  // once plan B is enqueued (its stream then waits on that plan's ready()), ahead of plans A and C:
+  // the G2 accumulation comes first in the proof.
   // ZKP_SERIAL=1 (profiling only) chains the three streams so every kernel runs alone.
   std::exception_ptr err[3];
   std::promise<void> planned;
@@ -617,20 +655,25 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
       HIPX(hipSetDevice(dev_));
       HIPX(hipStreamWaitEvent(s2_, ev_[EV_H2D_END], 0));
       HIPX(hipEventRecord(ev_[EV_G1_BEGIN], s2_));
-      HIPX(hipStreamWaitEvent(ws.plan->stream(), ev_[EV_H2D_END], 0));
-      ws.plan->build(d_wit + wlo_ * 8, whi_ - wlo_);
-      planned.set_value();
-      planned_set = true;
+      HIPX(hipStreamWaitEvent(ws.plan[PL_B]->stream(), ev_[EV_H2D_END], 0));
+      for (int p = 0; p < NPLAN; ++p) {
+        if (ws.own[p]) ws.own[p]->build(d_wit + wlo_ * 8, whi_ - wlo_, ws.mask[p], ws.present[p]);
+        if (p == PL_B) {
+          planned.set_value();
+          planned_set = true;
+        }
+      }
       const MsmBases* tabs[3] = {ws.ta.get(), ws.tb1.get(), ws.tc.get()};
+      const MsmPlan* plans[3] = {ws.plan[PL_A], ws.plan[PL_B], ws.plan[PL_C]};
       for (int m = 0; m < 3; ++m) {
         if (g2first && m == g2first - 1) {
           g2acc_f.get();
           HIPX(hipStreamWaitEvent(s2_, ev_[EV_G2_ACC], 0));
         }
-        ws.g1[m]->accumulate(*ws.plan, *tabs[m]);
+        ws.g1[m]->accumulate(*plans[m], *tabs[m]);
         HIPX(hipEventRecord(ev_[EV_ACC_A + m], s2_));
         HIPX(hipStreamWaitEvent(s3_, ev_[EV_ACC_A + m], 0));
-        ws.g1[m]->finish(*ws.plan, wa + m * wina_, s3_);
+        ws.g1[m]->finish(*plans[m], wa + m * wina_, s3_);
         if (serial_) {  // profiling: no overlap between the finish and the next accumulation
           HIPX(hipEventRecord(ev_[EV_FINISH], s3_));
           HIPX(hipStreamWaitEvent(s2_, ev_[EV_FINISH], 0));
@@ -650,13 +693,13 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
       HIPX(hipEventRecord(ev_[EV_G2_BEGIN], s1_));
       // the finish on s1 too: s3 is in-order, the G1 finishes must not queue behind it (gating the
       // G2 finish on the H plan, on either stream, measured +0.9 ms: profiles/g2_finish_r03.txt)
-      ws.g2->accumulate(*ws.plan, *ws.tb2);
+      ws.g2->accumulate(*ws.plan[PL_B], *ws.tb2);
       if (g2first) {
         HIPX(hipEventRecord(ev_[EV_G2_ACC], s1_));
         g2acc.set_value();
         g2acc_set = true;
       }
-      ws.g2->finish(*ws.plan, wb2, s1_);
+      ws.g2->finish(*ws.plan[PL_B], wb2, s1_);
       HIPX(hipEventRecord(ev_[EV_G2_END], s1_));
     } catch (...) {
       err[1] = std::current_exception();

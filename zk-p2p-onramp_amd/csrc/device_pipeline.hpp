@@ -55,10 +55,14 @@ int env_int(const char* name, int dflt);
 //   wsets=1|2             witness-MSM configurations kept resident (default 2: w and w2)
 //   wsel=first|second|auto  which one a proof takes (default auto: by the witness's share of values
 //                         >= 2^32, DevicePipeline::pick_wset)
+//   sparse=0|1            1 (default): a scalar whose base is the point at infinity emits no digit -- a
+//                         prover builds one witness plan per distinct mask of finite bases (B1 and B2
+//                         share one); 0: one unmasked witness plan for all four MSMs
 struct MsmOptions {
   int w = 0, h = 0, depth = 0, task_w = 0, task_h = 0, seg = 0, w2 = 0, wsets = 2;
   int dense = 1;
   int wsel = 0;  // 0 auto, 1 first, 2 second
+  int sparse = 1;
 };
 MsmOptions msm_options();
 
@@ -225,9 +229,9 @@ class DevicePipeline {
     out.insert(out.end(), launches_.begin(), launches_.end());
   }
   void msm_params(MsmParams& pw, MsmParams& ph, MsmParams* pw2 = nullptr) const {
-    pw = ws_[0].plan->params();
+    pw = ws_[0].pw;
     ph = plan_h_->params();
-    if (pw2) *pw2 = nws_ > 1 ? ws_[1].plan->params() : MsmParams{};
+    if (pw2) *pw2 = nws_ > 1 ? ws_[1].pw : MsmParams{};
   }
   int witness_sets() const { return nws_; }
   size_t table_bytes() const {
@@ -304,23 +308,33 @@ class DevicePipeline {
   };
   Event ev_[EV_COUNT];
   JobThread jt_g1_, jt_g2_;  // host threads feeding s2 (witness plan, G1 MSMs) and s1 (G2 MSM)
-  // one witness-MSM configuration (the witness plan serves A, B1, C and B2): window bits, base tables
-  // (shared by the pipelines of one device), plan and engines (per pipeline)
+  // one witness-MSM configuration: window bits, base tables and the mask of the bases finite in B1 or
+  // B2 (shared by the pipelines of one device), plans and engines (per pipeline).  A witness plan per
+  // distinct mask of finite bases, in the order the accumulations take them: B (B2 then B1), A, C;
+  // tables without a mask (and all of them under ZKP_MSM sparse=0) share one unmasked plan.  The
+  // plans build back to back on one stream and share the sort's scratch.
+  enum { PL_B, PL_A, PL_C, NPLAN };
   struct WSet {
     MsmParams pw;
     std::shared_ptr<MsmBases> ta, tb1, tc, tb2;
-    std::unique_ptr<MsmPlan> plan;
+    std::shared_ptr<BaseMask> mb;
+    std::unique_ptr<MsmPlan> own[NPLAN];  // own[p]: built for slot p (null: slot p uses an earlier one)
+    MsmPlan* plan[NPLAN] = {};            // the plan each slot takes
+    const uint32_t* mask[NPLAN] = {};  // each slot's index list of finite bases (null: no mask)
+    size_t present[NPLAN] = {};
     std::unique_ptr<MsmEngine> g1[3], g2;  // g1: A, B1, C
+    void drop_engines() {
+      for (int p = 0; p < NPLAN; ++p) own[p].reset(), plan[p] = nullptr;
+      for (auto& g : g1) g.reset();
+      g2.reset();
+    }
   };
   WSet ws_[2];
   int nws_ = 1, wsel_opt_ = 0;
+  bool sparse_ = true;         // ZKP_MSM sparse=
   bool wset2_tables_ = false;  // this device holds the second configuration's tables (add_second_wset)
   size_t nv_ = 0;              // witness signals of this pipeline's slice
-  void build_engines(WSet& w) {
-    w.plan = std::make_unique<MsmPlan>(nv_, w.pw, s3_);
-    for (auto& g : w.g1) g = std::make_unique<MsmEngine>(Curve::G1, w.pw, nv_, s2_);
-    w.g2 = std::make_unique<MsmEngine>(Curve::G2, w.pw, nv_, s1_);
-  }
+  void build_engines(WSet& w);
   std::shared_ptr<MsmBases> th_;  // shared by the pipelines of one device
   DevBuf<> rowptr_[2], col_[2], val_[2];
   static constexpr int NUP = 2;    // witness upload slots (double buffering)

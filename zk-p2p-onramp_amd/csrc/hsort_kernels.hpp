@@ -9,7 +9,8 @@
 // for the Venmo H plan (2^19 buckets) 7 + 7 + 5; b3 grows past 5 (tiled pass C) only for kb > 23.  Three MSD passes, every scatter staged in LDS
 // so that consecutive lanes write consecutive addresses of one destination run:
 //   A  k_hs_count1 / scan / k_hs_binbase / k_hs_scatter1
-//        digits computed from the scalars (zero digits dropped), grouped by bin: per (bin, block
+//        digits computed from the scalars (zero digits and, under a mask of finite bases, the scalars of
+//        the bases at infinity dropped), grouped by bin: per (bin, block
 //        of K * HS_TPB scalars, <= HS_STAGE entries) counts, their bin-major exclusive scan (every
 //        (bin, block) run's position), bin bases; a
 //        block's entries counted, scanned and placed in LDS, then written as runs (~52 entries
@@ -199,17 +200,21 @@ __global__ __launch_bounds__(SC_TPB) void k_lvl_apply(const uint32_t* __restrict
 }
 
 // ---------------------------------------------------------------- pass A: digits -> bins
-// a workgroup takes K * HS_TPB scalars (K * HS_TPB * W <= HS_STAGE entries), K per thread
-template <int K>
-__global__ __launch_bounds__(HS_TPB) void k_hs_count1(const uint32_t* __restrict__ scalars, uint32_t n, int c, int W,
+// a workgroup takes K * HS_TPB scalars (K * HS_TPB * W <= HS_STAGE entries), K per thread.
+// MASK: the m scalars index[0..m) are visited instead of all m = n -- the others' bases are the point
+// at infinity (msm.hpp BaseMask::list), they emit no digit; without MASK `index` is never read
+template <int K, bool MASK>
+__global__ __launch_bounds__(HS_TPB) void k_hs_count1(const uint32_t* __restrict__ scalars, uint32_t n,
+                                                      const uint32_t* __restrict__ index, uint32_t m, int c, int W,
                                                       int T, int sh1, uint32_t nbins, uint32_t* __restrict__ hist) {
   __shared__ uint32_t h[1 << HS_MAX_B1];
   for (uint32_t b = threadIdx.x; b < nbins; b += HS_TPB) h[b] = 0;
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < K; ++q) {
-    const uint32_t i = blockIdx.x * (K * HS_TPB) + q * HS_TPB + threadIdx.x;
-    if (i >= n) break;
+    const uint32_t j = blockIdx.x * (K * HS_TPB) + q * HS_TPB + threadIdx.x;
+    if (j >= m) break;
+    const uint32_t i = MASK ? index[j] : j;
     uint32_t s[9];
     msmk::load_scalar(scalars, i, s);
     uint32_t carry = 0;
@@ -246,9 +251,10 @@ __global__ __launch_bounds__(512) void k_hs_binbase(const uint32_t* __restrict__
 
 // the block's digits counted per bin, scanned, placed in an LDS stage grouped by bin (LDS
 // atomics), then the stage written out linearly: consecutive lanes, consecutive addresses of a run
-template <int K>
-__global__ __launch_bounds__(HS_TPB) void k_hs_scatter1(const uint32_t* __restrict__ scalars, uint32_t n, int c,
-                                                        int W, int T, int sh1, uint32_t nbins,
+template <int K, bool MASK>
+__global__ __launch_bounds__(HS_TPB) void k_hs_scatter1(const uint32_t* __restrict__ scalars, uint32_t n,
+                                                        const uint32_t* __restrict__ index, uint32_t m, int c, int W,
+                                                        int T, int sh1, uint32_t nbins,
                                                         const uint32_t* __restrict__ pos,
                                                         uint2* __restrict__ ent) {
   constexpr int NB = 1 << HS_MAX_B1;
@@ -266,9 +272,10 @@ __global__ __launch_bounds__(HS_TPB) void k_hs_scatter1(const uint32_t* __restri
   uint2 e[K][EM];
 #pragma unroll
   for (int q = 0; q < K; ++q) {
-    const uint32_t i = blockIdx.x * (K * HS_TPB) + q * HS_TPB + threadIdx.x;
+    const uint32_t j = blockIdx.x * (K * HS_TPB) + q * HS_TPB + threadIdx.x;
     uint32_t s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const bool act = i < n;
+    const bool act = j < m;
+    const uint32_t i = act && MASK ? index[j] : j;
     if (act) msmk::load_scalar(scalars, i, s);
     uint32_t carry = 0;
 #pragma unroll

@@ -32,6 +32,8 @@ struct MsmRig {
   DevBuf<> ds, dw;
   size_t n;
   Curve curve;
+  const uint32_t* present = nullptr;  // the table's list of finite bases (null: all are, or ZKP_MSM sparse=0)
+  size_t n_present = 0;
   float table_ms = 0;  // base-table build: row 0 upload + conversion + the derived rows (HIP events)
   MsmRig(int device, Curve cv, const uint8_t* points, const uint8_t* scalars, size_t n_, int c, int depth)
       : n(n_), curve(cv) {
@@ -49,7 +51,9 @@ struct MsmRig {
     apply_task_options(prm, opt.task_h, opt);  // the H plan's task size too (choose_msm_params)
     bases = std::make_unique<MsmBases>(curve, n, prm.c, prm.depth);
     table_ms = time_on(st, 1, [&] { fill_bases(*bases, points, n, 0, st); });
-    plan = std::make_unique<MsmPlan>(std::max<size_t>(n, 1), prm, st);
+    if (opt.sparse) present = bases->present_index();
+    n_present = present ? bases->present_count() : n;
+    plan = std::make_unique<MsmPlan>(std::max<size_t>(n, 1), prm, st, n_present);
     plan->set_dense(opt.dense != 0);
     eng = std::make_unique<MsmEngine>(curve, prm, std::max<size_t>(n, 1), st);
     ds = DevBuf<>(std::max<size_t>(n * 8, 8));
@@ -57,7 +61,7 @@ struct MsmRig {
     if (n) HIPX(hipMemcpyAsync(ds, scalars, n * 32, hipMemcpyHostToDevice, st));
   }
   void run() {
-    plan->build(ds, n);
+    plan->build(ds, n, present, n_present);
     eng->run(*plan, *bases, dw);
   }
   // fold the group sums and write the affine result (standard-form LE)

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "curve.hpp"
 #include "msm_kernels.hpp"
@@ -27,6 +28,37 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t m) {  // set bits of m be
 template <class F>
 __global__ __launch_bounds__(TPB) void k_extend_row(uint32_t* __restrict__ table, uint32_t n, int dbl, int t) {
   msmk::extend_row<F>(blockIdx.x * TPB + threadIdx.x, table, n, dbl, t);
+}
+
+// the mask of the finite bases of row 0 (BaseMask): thread i tests base i (PW words: all zero = the
+// point at infinity, in the zkey's form and in the device's), a wave's ballot gives two mask words;
+// count += the finite bases
+template <int PW>
+__global__ __launch_bounds__(TPB) void k_present(const uint32_t* __restrict__ row0, uint32_t n,
+                                                 uint32_t* __restrict__ bits, uint32_t* __restrict__ count) {
+  const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+  uint32_t any = 0;
+  if (i < n) {
+    const uint4* p = reinterpret_cast<const uint4*>(row0 + (size_t)i * PW);
+#pragma unroll
+    for (int q = 0; q < PW / 4; ++q) {
+      const uint4 v = p[q];
+      any |= v.x | v.y | v.z | v.w;
+    }
+  }
+  const uint64_t m = __ballot(any != 0);
+  const uint32_t lane = threadIdx.x & 63;
+  if ((lane & 31) == 0 && i < n) bits[i >> 5] = (uint32_t)(m >> lane);
+  if (lane == 0 && m) atomicAdd(count, (uint32_t)__popcll(m));
+}
+__global__ __launch_bounds__(TPB) void k_mask_or(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                 uint32_t nw, uint32_t* __restrict__ out,
+                                                 uint32_t* __restrict__ count) {
+  const uint32_t j = blockIdx.x * TPB + threadIdx.x;
+  if (j >= nw) return;
+  const uint32_t v = a[j] | b[j];
+  out[j] = v;
+  if (v) atomicAdd(count, (uint32_t)__popc(v));
 }
 
 // G2 (Fq2) accumulation and bucket merges (the wide finish kernels): without a bound the
@@ -216,167 +248,250 @@ MsmBases::MsmBases(Curve curve, size_t n, int c, int depth) : curve_(curve), n_(
   d_ = DevBuf<>(bytes_ / 4);
 }
 
+namespace {
+
+// the count of a mask just enqueued on st comes to the host; a mask with every bit set is dropped,
+// any other gets its index list (built on the host: once per table, at load)
+void settle_mask(BaseMask& m, const uint32_t* d_count, size_t n, hipStream_t st) {
+  uint32_t cnt = 0;
+  HIPX(hipGetLastError());
+  HIPX(hipMemcpyAsync(&cnt, d_count, 4, hipMemcpyDeviceToHost, st));
+  HIPX(hipStreamSynchronize(st));
+  m.count = cnt;
+  if (cnt == n) {
+    m.bits.reset();
+    return;
+  }
+  if (cnt == 0) {  // nothing to list: a plan still sees a mask, of no scalars
+    m.index = DevBuf<>(1);
+    return;
+  }
+  std::vector<uint32_t> bits((n + 31) / 32), idx;
+  HIPX(hipMemcpy(bits.data(), m.bits, bits.size() * 4, hipMemcpyDeviceToHost));
+  idx.reserve(cnt);
+  for (size_t w = 0; w < bits.size(); ++w)
+    for (uint32_t v = bits[w]; v; v &= v - 1) idx.push_back((uint32_t)(w * 32 + __builtin_ctz(v)));
+  if (idx.size() != cnt) throw std::runtime_error("MSM: mask and its count disagree");
+  m.index = DevBuf<>(cnt);
+  HIPX(hipMemcpy(m.index, idx.data(), (size_t)cnt * 4, hipMemcpyHostToDevice));
+}
+
+}  // namespace
+
 void MsmBases::extend(hipStream_t st) {
+  mask_ = BaseMask{};
   if (n_ == 0) return;
+  mask_.bits = DevBuf<>((n_ + 31) / 32);
+  DevBuf<> cnt(1);
+  HIPX(hipMemsetAsync(cnt, 0, 4, st));
+  if (curve_ == Curve::G1)
+    hipLaunchKernelGGL(k_present<16>, dim3(grid_for(n_)), dim3(TPB), 0, st, d_, (uint32_t)n_, mask_.bits, cnt);
+  else
+    hipLaunchKernelGGL(k_present<32>, dim3(grid_for(n_)), dim3(TPB), 0, st, d_, (uint32_t)n_, mask_.bits, cnt);
   for (int t = 1; t < depth_; ++t) {
     if (curve_ == Curve::G1)
       hipLaunchKernelGGL(k_extend_row<Fq>, dim3(grid_for(n_)), dim3(TPB), 0, st, d_, (uint32_t)n_, c_, t);
     else
       hipLaunchKernelGGL(k_extend_row<Fq2>, dim3(grid_for(n_)), dim3(TPB), 0, st, d_, (uint32_t)n_, c_, t);
   }
-  HIPX(hipGetLastError());
+  settle_mask(mask_, cnt, n_, st);
+}
+
+BaseMask mask_union(const MsmBases& a, const MsmBases& b, hipStream_t st) {
+  if (a.n() != b.n()) throw std::runtime_error("MSM: mask union of tables of different sizes");
+  BaseMask m;
+  m.count = a.n();
+  if (!a.present() || !b.present()) return m;
+  const size_t nw = (a.n() + 31) / 32;
+  m.bits = DevBuf<>(nw);
+  DevBuf<> cnt(1);
+  HIPX(hipMemsetAsync(cnt, 0, 4, st));
+  hipLaunchKernelGGL(k_mask_or, dim3(grid_for(nw)), dim3(TPB), 0, st, a.present(), b.present(), (uint32_t)nw,
+                     m.bits, cnt);
+  settle_mask(m, cnt, a.n(), st);
+  return m;
 }
 
 // ------------------------------------------------------------------ MsmPlan
 
-MsmPlan::MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream)
-    : prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream) {
-  if (prm_.c < MsmParams::MIN_C || prm_.c > MsmParams::MAX_C || prm_.windows > HS_STAGE / HS_TPB)
+MsmSortScratch::MsmSortScratch(size_t max_n_, size_t max_present, const MsmParams& prm_)
+    : prm(prm_), max_n(std::max<size_t>(max_n_, 1)) {
+  if (prm.c < MsmParams::MIN_C || prm.c > MsmParams::MAX_C || prm.windows > HS_STAGE / HS_TPB)
     throw std::invalid_argument("MSM: window bits outside the plan's range");
-  if (max_n_ * prm_.depth >= (size_t(1) << 31)) throw std::runtime_error("MSM size too large for 31-bit base indices");
-  nbuckets_ = prm_.buckets();
-  max_entries_ = max_n_ * prm_.windows;
-  if (max_entries_ >= 0xffffffffull) throw std::runtime_error("MSM size too large for 32-bit entry indices");
-  max_tasks_ = (max_entries_ + prm_.S - 1) / prm_.S + nbuckets_;
-  merge_levels_ = msm_merge_levels(max_n_, prm_);
-  vals_sorted_ = DevBuf<>(max_entries_);
-  bstart_ = DevBuf<>(nbuckets_ + 1);
-  bend_ = DevBuf<>(nbuckets_ + 1);
-  cnt_ = DevBuf<>(nbuckets_ + 1);
-  off_task_ = DevBuf<>(nbuckets_ + 1);
-  perm_ = DevBuf<>(max_tasks_);
-  const size_t ntl = (size_t)(prm_.S + 1) * grid_for(max_tasks_);
-  tl_hist_ = DevBuf<>(ntl);
-  tl_off_ = DevBuf<>(ntl);
-  if (merge_levels_ > 0) {
-    lvl_all_ = DevBuf<>((size_t)merge_levels_ * (nbuckets_ + 1));
-    lvl_tsum_ = DevBuf<>((size_t)merge_levels_ * scan_tiles_for(nbuckets_ + 1));
-  }
+  if (max_n * prm.depth >= (size_t(1) << 31)) throw std::runtime_error("MSM size too large for 31-bit base indices");
+  nbuckets = prm.buckets();
+  max_entries = std::max<size_t>(std::min(max_present, max_n), 1) * prm.windows;
+  if (max_entries >= 0xffffffffull) throw std::runtime_error("MSM size too large for 32-bit entry indices");
+  max_tasks = (max_entries + prm.S - 1) / prm.S + nbuckets;
+  merge_levels = msm_merge_levels(max_n, prm);
+  cnt = DevBuf<>(nbuckets + 1);
+  const size_t ntl = (size_t)(prm.S + 1) * grid_for(max_tasks);
+  tl_hist = DevBuf<>(ntl);
+  tl_off = DevBuf<>(ntl);
+  if (merge_levels > 0) lvl_tsum = DevBuf<>((size_t)merge_levels * scan_tiles_for(nbuckets + 1));
   // bucket-key bits kb = b1 (bin) + b2 (sub-bin) + b3 (bucket in sub-bin): b3 = 5 for the one-
   // workgroup-per-sub-bin pass C (k_hs_fine), up to 9 (tiled pass C) when kb > 23 (c > 20 with
   // several bucket groups); b1, b2 <= 9
   int kb = 1;
-  while ((size_t(1) << kb) < nbuckets_) ++kb;
-  hs_b3_ = std::max(std::min(kb, HS_B3), kb - HS_MAX_B1 - HS_MAX_B2);
-  hs_b2_ = (kb - hs_b3_) / 2;
-  const int b1 = kb - hs_b3_ - hs_b2_;
-  if (b1 > HS_MAX_B1 || hs_b2_ > HS_MAX_B2 || hs_b3_ > HS_MAX_B2)
+  while ((size_t(1) << kb) < nbuckets) ++kb;
+  b3 = std::max(std::min(kb, HS_B3), kb - HS_MAX_B1 - HS_MAX_B2);
+  b2 = (kb - b3) / 2;
+  const int b1 = kb - b3 - b2;
+  if (b1 > HS_MAX_B1 || b2 > HS_MAX_B2 || b3 > HS_MAX_B2)
     throw std::invalid_argument("MSM: too many buckets for the bucket sort (window bits x bucket groups)");
-  hs_nbins_ = (uint32_t)((nbuckets_ + (size_t(1) << (hs_b2_ + hs_b3_)) - 1) >> (hs_b2_ + hs_b3_));
-  hs_k_ = std::max(1, std::min(4, HS_STAGE / (HS_TPB * prm_.windows)));
-  if (hs_k_ == 3) hs_k_ = 2;
-  hs_nblk_ = (uint32_t)((max_n_ + hs_k_ * HS_TPB - 1) / (hs_k_ * HS_TPB));
-  hs_max_tiles_ = (uint32_t)((max_entries_ + HS_TILE - 1) / HS_TILE + hs_nbins_);
-  const uint32_t nq = hs_nbins_ << hs_b2_;
-  hs_max_tiles3_ = (uint32_t)((max_entries_ + HS_TILE - 1) / HS_TILE + nq);
-  const size_t nh3 = ((size_t)hs_max_tiles3_ << hs_b3_) + 1;
-  hs_toff3_ = DevBuf<>((size_t)nq + 1);
-  hs_hist3_ = DevBuf<>(nh3);
-  hs_off3_ = DevBuf<>(nh3);
-  const size_t nh = (size_t)hs_nbins_ * hs_nblk_, nh2 = (size_t)hs_max_tiles_ << hs_b2_;
-  hs_hist_ = DevBuf<>(nh);
-  hs_blkoff_ = DevBuf<>(nh);
-  hs_binbase_ = DevBuf<>(hs_nbins_ + 1);
-  hs_toff_ = DevBuf<>(hs_nbins_ + 1);
-  hs_hist2_ = DevBuf<>(nh2);
-  hs_off2_ = DevBuf<>(nh2);
-  hs_subbase_ = DevBuf<>((size_t)nq + 1);
-  hs_ent_a_ = DevBuf<uint2>(max_entries_);
-  hs_ent_b_ = DevBuf<uint2>(max_entries_);
-  const size_t scan_n = std::max(std::max(std::max(nbuckets_ + 1, nh3), std::max(nh2, ntl)), nh);
-  tsum_ = DevBuf<>(scan_tiles_for(scan_n) + 1);
+  nbins = (uint32_t)((nbuckets + (size_t(1) << (b2 + b3)) - 1) >> (b2 + b3));
+  k = std::max(1, std::min(4, HS_STAGE / (HS_TPB * prm.windows)));
+  if (k == 3) k = 2;
+  const uint32_t nblk = (uint32_t)((max_n + k * HS_TPB - 1) / (k * HS_TPB));
+  const uint32_t max_tiles = (uint32_t)((max_entries + HS_TILE - 1) / HS_TILE + nbins);
+  const uint32_t nq = nbins << b2;
+  const uint32_t max_tiles3 = (uint32_t)((max_entries + HS_TILE - 1) / HS_TILE + nq);
+  const size_t nh3 = ((size_t)max_tiles3 << b3) + 1;
+  toff3 = DevBuf<>((size_t)nq + 1);
+  hist3 = DevBuf<>(nh3);
+  off3 = DevBuf<>(nh3);
+  const size_t nh = (size_t)nbins * nblk, nh2 = (size_t)max_tiles << b2;
+  hist = DevBuf<>(nh);
+  blkoff = DevBuf<>(nh);
+  toff = DevBuf<>(nbins + 1);
+  hist2 = DevBuf<>(nh2);
+  off2 = DevBuf<>(nh2);
+  subbase = DevBuf<>((size_t)nq + 1);
+  ent_a = DevBuf<uint2>(max_entries);
+  ent_b = DevBuf<uint2>(max_entries);
+  const size_t scan_n = std::max(std::max(std::max(nbuckets + 1, nh3), std::max(nh2, ntl)), nh);
+  tsum = DevBuf<>(scan_tiles_for(scan_n) + 1);
+}
+
+MsmPlan::MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream, size_t max_present,
+                 std::shared_ptr<MsmSortScratch> scratch)
+    : prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream), sc_(std::move(scratch)) {
+  if (!sc_) sc_ = std::make_shared<MsmSortScratch>(max_n_, max_present, prm_);
+  nbuckets_ = prm_.buckets();
+  max_entries_ = std::max<size_t>(std::min(max_present, max_n_), 1) * prm_.windows;
+  const MsmParams& q = sc_->prm;
+  if (q.c != prm_.c || q.windows != prm_.windows || q.depth != prm_.depth || q.S != prm_.S || sc_->max_n < max_n_ ||
+      sc_->max_entries < max_entries_)
+    throw std::runtime_error("MSM: sort scratch built for other parameters or fewer entries");
+  max_tasks_ = (max_entries_ + prm_.S - 1) / prm_.S + nbuckets_;
+  merge_levels_ = sc_->merge_levels;
+  vals_sorted_ = DevBuf<>(max_entries_);
+  bstart_ = DevBuf<>(nbuckets_ + 1);
+  bend_ = DevBuf<>(nbuckets_ + 1);
+  off_task_ = DevBuf<>(nbuckets_ + 1);
+  perm_ = DevBuf<>(max_tasks_);
+  if (merge_levels_ > 0) lvl_all_ = DevBuf<>((size_t)merge_levels_ * (nbuckets_ + 1));
+  hs_binbase_ = DevBuf<>(sc_->nbins + 1);
   ready_ = Event(false);
 }
 
-void MsmPlan::build(const uint32_t* scalars, size_t n) {
+// pass A's kernels for K scalars per thread, with (MASK) or without a mask of finite bases
+template <bool MASK>
+static auto hs_count1_for(int k) {
+  return k == 4 ? k_hs_count1<4, MASK> : (k == 2 ? k_hs_count1<2, MASK> : k_hs_count1<1, MASK>);
+}
+template <bool MASK>
+static auto hs_scatter1_for(int k) {
+  return k == 4 ? k_hs_scatter1<4, MASK> : (k == 2 ? k_hs_scatter1<2, MASK> : k_hs_scatter1<1, MASK>);
+}
+
+void MsmPlan::build(const uint32_t* scalars, size_t n, const uint32_t* present, size_t n_present) {
   if (n > max_n_) throw std::runtime_error("MSM: n exceeds plan capacity");
+  if (!present) n_present = n;
+  if (n_present > n) throw std::runtime_error("MSM: more finite bases than scalars");
+  if (n_present * prm_.windows > max_entries_) throw std::runtime_error("MSM: finite bases exceed plan capacity");
   n_ = n;
+  MsmSortScratch& sc = *sc_;
   const uint32_t W = (uint32_t)prm_.windows;
   const uint32_t nb = (uint32_t)nbuckets_;
+  const int hs_b2_ = sc.b2, hs_b3_ = sc.b3;
+  const uint32_t hs_nbins_ = sc.nbins;
   hipStream_t st = stream_;
-  // total_ = n * W bounds the nonzero digits (the accumulate grid: threads past the last task exit),
-  // so nothing waits on the host; the exact count stays on the device (entries_dev)
-  total_ = (uint32_t)(n * W);
+  // total_ = n * W (with a mask: its count * W) bounds the nonzero digits (the accumulate grid: threads
+  // past the last task exit), so nothing waits on the host; the exact count stays on the device
+  // (entries_dev)
+  total_ = (uint32_t)(n_present * W);
   hs_built_ = false;
   if (total_ == 0) {
     HIPX(hipMemsetAsync(bstart_, 0, (nbuckets_ + 1) * 4, st));
     HIPX(hipMemsetAsync(bend_, 0, (nbuckets_ + 1) * 4, st));
-    HIPX(hipMemsetAsync(cnt_, 0, (nbuckets_ + 1) * 4, st));
+    HIPX(hipMemsetAsync(sc.cnt, 0, (nbuckets_ + 1) * 4, st));
   } else {
-    // the hand-written three-pass LDS-staged bucket sort (hsort_kernels.hpp), zero digits dropped in
-    // pass A.  Dense plans (uniform scalars: the H MSM) group their sub-bins with one workgroup each
+    // the hand-written three-pass LDS-staged bucket sort (hsort_kernels.hpp), zero digits and the
+    // scalars whose base is at infinity dropped in pass A (it visits only the mask's index list).  Dense plans (uniform scalars: the H MSM) group their sub-bins with one workgroup each
     // (k_hs_fine); compacted plans (the witness: whole waves of one bin / sub-bin / bucket) take the
     // wave-aggregated LDS claims and the tiled pass C, as do keys with more than 5 bucket bits per
     // sub-bin
-    const int k = hs_k_;
-    const uint32_t nblk = (uint32_t)((n + k * HS_TPB - 1) / (k * HS_TPB)), nsub = 1u << hs_b2_;
+    const int k = sc.k;
+    // pass A visits the scalars the mask lists (all n without one)
+    const uint32_t nblk = (uint32_t)((n_present + k * HS_TPB - 1) / (k * HS_TPB)), nsub = 1u << hs_b2_;
     const int sh1 = hs_b2_ + hs_b3_;
-    uint2* ea = hs_ent_a_;
-    uint2* eb = hs_ent_b_;
+    uint2* ea = sc.ent_a;
+    uint2* eb = sc.ent_b;
     // A: digits -> bins
-    auto count1 = k == 4 ? k_hs_count1<4> : (k == 2 ? k_hs_count1<2> : k_hs_count1<1>);
-    hipLaunchKernelGGL(count1, dim3(nblk), dim3(HS_TPB), 0, st, scalars, (uint32_t)n, prm_.c, (int)W, prm_.depth, sh1,
-                       hs_nbins_, hs_hist_);
-    scan_nolookback(hs_hist_, hs_blkoff_, (size_t)hs_nbins_ * nblk, tsum_, st);
-    hipLaunchKernelGGL(k_hs_binbase, dim3(1), dim3(512), 0, st, hs_blkoff_, hs_hist_, hs_nbins_, nblk, hs_binbase_,
-                       hs_toff_);
-    auto scatter1 = k == 4 ? k_hs_scatter1<4> : (k == 2 ? k_hs_scatter1<2> : k_hs_scatter1<1>);
+    auto count1 = present ? hs_count1_for<true>(k) : hs_count1_for<false>(k);
+    hipLaunchKernelGGL(count1, dim3(nblk), dim3(HS_TPB), 0, st, scalars, (uint32_t)n, present,
+                       (uint32_t)n_present, prm_.c, (int)W, prm_.depth, sh1, hs_nbins_, sc.hist);
+    scan_nolookback(sc.hist, sc.blkoff, (size_t)hs_nbins_ * nblk, sc.tsum, st);
+    hipLaunchKernelGGL(k_hs_binbase, dim3(1), dim3(512), 0, st, sc.blkoff, sc.hist, hs_nbins_, nblk, hs_binbase_,
+                       sc.toff);
+    auto scatter1 = present ? hs_scatter1_for<true>(k) : hs_scatter1_for<false>(k);
     const size_t lds1 = (size_t)k * HS_TPB * W * 8 + (size_t)hs_nbins_ * 8;
-    hipLaunchKernelGGL(scatter1, dim3(nblk), dim3(HS_TPB), lds1, st, scalars, (uint32_t)n, prm_.c, (int)W, prm_.depth,
-                       sh1, hs_nbins_, hs_blkoff_, ea);
+    hipLaunchKernelGGL(scatter1, dim3(nblk), dim3(HS_TPB), lds1, st, scalars, (uint32_t)n, present,
+                       (uint32_t)n_present, prm_.c, (int)W, prm_.depth, sh1, hs_nbins_, sc.blkoff, ea);
     // B: bins -> sub-bins (tiles past the used ones exit; their counters stay zero)
     const size_t tiles = ((size_t)total_ + HS_TILE - 1) / HS_TILE + hs_nbins_;
     const size_t nh2 = tiles << hs_b2_;
-    HIPX(hipMemsetAsync(hs_hist2_, 0, nh2 * 4, st));
+    HIPX(hipMemsetAsync(sc.hist2, 0, nh2 * 4, st));
     const bool skew = !dense_;
     hipLaunchKernelGGL((skew ? k_hs_count2<true> : k_hs_count2<false>), dim3((unsigned)tiles), dim3(HS_TPB), 0, st, ea,
-                       hs_binbase_, hs_toff_, hs_nbins_, hs_b3_, nsub, hs_hist2_);
-    scan_nolookback(hs_hist2_, hs_off2_, nh2, tsum_, st);
+                       hs_binbase_, sc.toff, hs_nbins_, hs_b3_, nsub, sc.hist2);
+    scan_nolookback(sc.hist2, sc.off2, nh2, sc.tsum, st);
     const uint32_t nq = hs_nbins_ * nsub;
-    hipLaunchKernelGGL(k_hs_subbase, dim3(grid_for(nq + 1)), dim3(HS_TPB), 0, st, hs_off2_, hs_binbase_, hs_toff_,
-                       hs_nbins_, nsub, hs_subbase_);
+    hipLaunchKernelGGL(k_hs_subbase, dim3(grid_for(nq + 1)), dim3(HS_TPB), 0, st, sc.off2, hs_binbase_, sc.toff,
+                       hs_nbins_, nsub, sc.subbase);
     hipLaunchKernelGGL((skew ? k_hs_scatter2<true, false> : k_hs_scatter2<false, false>), dim3((unsigned)tiles),
-                       dim3(HS_TPB), 0, st, ea, hs_binbase_, hs_toff_, hs_nbins_, hs_b3_, nsub, hs_off2_, eb, nullptr);
+                       dim3(HS_TPB), 0, st, ea, hs_binbase_, sc.toff, hs_nbins_, hs_b3_, nsub, sc.off2, eb, nullptr);
     // C: sub-bins -> buckets, bounds and task counts
     if (dense_ && hs_b3_ <= HS_B3) {
-      hipLaunchKernelGGL(k_hs_fine, dim3(nq), dim3(HS_FINE_TPB), 0, st, eb, hs_subbase_, nq, hs_b3_, nb,
-                         (uint32_t)prm_.S, vals_sorted_, bstart_, bend_, cnt_);
+      hipLaunchKernelGGL(k_hs_fine, dim3(nq), dim3(HS_FINE_TPB), 0, st, eb, sc.subbase, nq, hs_b3_, nb,
+                         (uint32_t)prm_.S, vals_sorted_, bstart_, bend_, sc.cnt);
     } else {  // tiled: pass B one level down (no workgroup takes more than HS_TILE entries)
       const uint32_t nf = 1u << hs_b3_;
-      hipLaunchKernelGGL(k_hs_subtiles, dim3(1), dim3(SC_TPB), 0, st, hs_subbase_, nq, hs_toff3_);
+      hipLaunchKernelGGL(k_hs_subtiles, dim3(1), dim3(SC_TPB), 0, st, sc.subbase, nq, sc.toff3);
       const size_t tiles3 = ((size_t)total_ + HS_TILE - 1) / HS_TILE + nq, nh3 = tiles3 << hs_b3_;
-      HIPX(hipMemsetAsync(hs_hist3_, 0, nh3 * 4, st));
-      hipLaunchKernelGGL(k_hs_count2<true>, dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, hs_subbase_, hs_toff3_, nq,
-                         0, nf, hs_hist3_);
-      scan_nolookback(hs_hist3_, hs_off3_, nh3, tsum_, st);
-      hipLaunchKernelGGL((k_hs_scatter2<true, true>), dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, hs_subbase_,
-                         hs_toff3_, nq, 0, nf, hs_off3_, nullptr, vals_sorted_);
-      hipLaunchKernelGGL(k_hs_bounds3, dim3(grid_for((size_t)nb + 1)), dim3(HS_TPB), 0, st, hs_toff3_, hs_off3_,
-                         hs_subbase_, hs_b3_, nb, (uint32_t)prm_.S, bstart_, bend_, cnt_);
+      HIPX(hipMemsetAsync(sc.hist3, 0, nh3 * 4, st));
+      hipLaunchKernelGGL(k_hs_count2<true>, dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, sc.subbase, sc.toff3, nq,
+                         0, nf, sc.hist3);
+      scan_nolookback(sc.hist3, sc.off3, nh3, sc.tsum, st);
+      hipLaunchKernelGGL((k_hs_scatter2<true, true>), dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, sc.subbase,
+                         sc.toff3, nq, 0, nf, sc.off3, nullptr, vals_sorted_);
+      hipLaunchKernelGGL(k_hs_bounds3, dim3(grid_for((size_t)nb + 1)), dim3(HS_TPB), 0, st, sc.toff3, sc.off3,
+                         sc.subbase, hs_b3_, nb, (uint32_t)prm_.S, bstart_, bend_, sc.cnt);
     }
     hs_built_ = true;
   }
   // accumulate-task offsets and the heavy-bucket merge levels' offsets (look-back-free scans: they
   // run beside the accumulations of the other streams)
-  scan_nolookback(cnt_, off_task_, nbuckets_ + 1, tsum_, st);
+  scan_nolookback(sc.cnt, off_task_, nbuckets_ + 1, sc.tsum, st);
   max_tasks_now_ = ((size_t)total_ + prm_.S - 1) / prm_.S + nbuckets_;
   if (total_ > 0) {
     // accumulate-task order by length, longest first
     const unsigned nblk = grid_for(max_tasks_now_);
     const size_t lds = (size_t)(prm_.S + 1) * 4, nh = (size_t)(prm_.S + 1) * nblk;
     hipLaunchKernelGGL(k_tlen_count, dim3(nblk), dim3(TPB), lds, st, bstart_, bend_, off_task_, nb, (uint32_t)prm_.S,
-                       tl_hist_);
-    scan_nolookback(tl_hist_, tl_off_, nh, tsum_, st);
+                       sc.tl_hist);
+    scan_nolookback(sc.tl_hist, sc.tl_off, nh, sc.tsum, st);
     hipLaunchKernelGGL(k_tlen_scatter, dim3(nblk), dim3(TPB), lds, st, bstart_, bend_, off_task_, nb,
-                       (uint32_t)prm_.S, tl_off_, perm_);
+                       (uint32_t)prm_.S, sc.tl_off, perm_);
   }
   if (merge_levels_ > 0 && total_ > 0) {
     const uint32_t nt = (uint32_t)scan_tiles_for(nbuckets_ + 1);
     hipLaunchKernelGGL(k_lvl_tiles, dim3(nt), dim3(SC_TPB), 0, st, off_task_, nb, (uint32_t)prm_.S2, merge_levels_,
-                       nt, lvl_tsum_);
-    hipLaunchKernelGGL(k_lvl_top, dim3(merge_levels_), dim3(SC_TPB), 0, st, lvl_tsum_, nt);
+                       nt, sc.lvl_tsum);
+    hipLaunchKernelGGL(k_lvl_top, dim3(merge_levels_), dim3(SC_TPB), 0, st, sc.lvl_tsum, nt);
     hipLaunchKernelGGL(k_lvl_apply, dim3(nt), dim3(SC_TPB), 0, st, off_task_, nb, (uint32_t)prm_.S2, merge_levels_,
-                       nt, lvl_tsum_, lvl_all_);
+                       nt, sc.lvl_tsum, lvl_all_);
   }
   HIPX(hipGetLastError());
   HIPX(hipEventRecord(ready_, st));

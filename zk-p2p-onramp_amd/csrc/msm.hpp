@@ -12,8 +12,9 @@
 //     and the host Horner fold disappear; with T < W the W windows fall into
 //     G = ceil(W/T) bucket groups, folded by Horner with shift c*T.
 //
-//  MsmPlan   (per scalar vector, per proof; shared by every MSM over the same
-//     scalars -- A, B1, C and the G2 MSM B2 all use the witness)
+//  MsmPlan   (per scalar vector and set of finite bases, per proof; shared by every MSM over the
+//     same scalars and the same finite bases -- B1 and the G2 MSM B2 share the witness's plan B)
+//     0. mask   : a scalar whose base is the point at infinity (MsmBases::present) emits no digit
 //     1. digits : the nonzero signed c-bit digits as (key = group*2^(c-1) + |d|-1,
 //                 val = (t*n + i) | sign<<31), computed from the scalars inside
 //     2. sort   : the hand-written three-pass LDS-staged bucket sort (hsort_kernels.hpp)
@@ -37,6 +38,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -110,13 +112,33 @@ enum class Curve { G1 = 1, G2 = 2 };
 
 inline int curve_fwords(Curve c) { return c == Curve::G1 ? 8 : 16; }
 
+// The finite bases of a table as a device bitset: bit i & 31 of word i / 32 is set when base i is not
+// the point at infinity (all-zero coordinates).  A zkey holds an infinity base for every signal that no
+// A (or B) linear combination mentions; a plan built with the mask emits no digit for those, so the
+// accumulation never spends a wave's full addition on lanes that add nothing.  `index` lists the set
+// bits in order (index[j] = the j-th finite base): a masked plan's pass A visits `count` scalars through
+// it instead of testing n bits, so its cost follows the finite bases, not the signals.  Empty (no bits,
+// no index, both null) when every base is finite: a plan then runs its unmasked kernels and reads
+// neither.
+struct BaseMask {
+  DevBuf<> bits, index;
+  size_t count = 0;  // finite bases (n when there is no mask)
+  const uint32_t* data() const { return bits ? bits.get() : nullptr; }
+  const uint32_t* list() const { return index ? index.get() : nullptr; }
+};
+
 // Precomputed base table: rows() x n affine points (device layout, Montgomery R'=2^261).
 class MsmBases {
  public:
   MsmBases(Curve curve, size_t n, int c, int depth);
-  // row 0 (n points): the caller fills it (device layout), then extend() derives rows 1..T-1
+  // row 0 (n points): the caller fills it (device layout), then extend() derives rows 1..T-1 and the
+  // mask of the finite bases from row 0 (it waits for the stream once: the count comes to the host)
   uint32_t* row0() { return d_; }
   void extend(hipStream_t st);
+  // the finite bases (null: all of them) and how many they are, once extend() has run
+  const uint32_t* present() const { return mask_.data(); }
+  const uint32_t* present_index() const { return mask_.list(); }
+  size_t present_count() const { return mask_.bits ? mask_.count : n_; }
   const uint32_t* data() const { return d_; }
   size_t n() const { return n_; }
   int c() const { return c_; }
@@ -133,16 +155,44 @@ class MsmBases {
   int c_, depth_;
   size_t bytes_ = 0;
   DevBuf<> d_;
+  BaseMask mask_;
+};
+
+// the bases finite in a or in b (two tables over the same n signals whose MSMs share one plan: the
+// zkey's B1 and B2); no mask when either table has none.  Waits for the stream once.
+BaseMask mask_union(const MsmBases& a, const MsmBases& b, hipStream_t st);
+
+// The bucket sort's working memory and geometry: entries, histograms, tile offsets and scan sums,
+// 16 of a plan's ~20 bytes per entry.  Nothing reads it once MsmPlan::build has enqueued its last
+// kernel, so plans with the same parameters that build back to back on ONE stream share one.
+struct MsmSortScratch {
+  // max_n scalars of which at most max_present emit digits
+  MsmSortScratch(size_t max_n, size_t max_present, const MsmParams& prm);
+  MsmParams prm;
+  size_t max_n, max_entries, max_tasks, nbuckets;
+  int merge_levels = 0;
+  int b2 = 0, b3 = 0, k = 1;  // sub-bin / bucket bits of the key, scalars per thread in pass A
+  uint32_t nbins = 0;
+  DevBuf<> cnt, tl_hist, tl_off, lvl_tsum;
+  DevBuf<> toff3, hist3, off3;
+  DevBuf<> hist, blkoff, toff, hist2, off2, subbase;
+  DevBuf<uint2> ent_a, ent_b;  // (key, base|sign) entries
+  DevBuf<> tsum;               // tile sums of the look-back-free scans
 };
 
 class MsmPlan {
  public:
-  MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream);
+  // max_present: the most scalars that can emit digits (a mask's count; default all max_n), which
+  // sizes the plan's outputs; scratch: shared sort memory (see MsmSortScratch), or the plan's own
+  MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream, size_t max_present = ~size_t(0),
+          std::shared_ptr<MsmSortScratch> scratch = nullptr);
   // scalars: device, 8 LE 32-bit words each (standard form, any value < 2^256: reduced below r
   // when loaded, msm_kernels.hpp load_scalar, so W = ceil(255 / c) windows always hold the carry).
+  // present: the index list of a base table's mask over the same n (BaseMask::list; null = none) with
+  // n_present entries: a scalar it does not list counts as zero.
   // Enqueues on the plan's stream, never blocks the host (the exact entry count stays on the
   // device: entries_dev()); records ready() at the end.
-  void build(const uint32_t* scalars, size_t n);
+  void build(const uint32_t* scalars, size_t n, const uint32_t* present = nullptr, size_t n_present = 0);
   // dense (uniform scalars, e.g. the H MSM's: nearly every digit is nonzero and the buckets evenly
   // filled): pass C of the sort takes one workgroup per sub-bin; otherwise (the 0/1-heavy witness:
   // whole waves of entries in one bucket) wave-aggregated LDS claims and a tiled pass C
@@ -153,10 +203,11 @@ class MsmPlan {
   hipStream_t stream() const { return stream_; }
   size_t n() const { return n_; }
   size_t max_n() const { return max_n_; }
-  // entries the accumulate grid is sized for: the bound n * W (the exact count stays on the device)
+  // entries the accumulate grid is sized for: the bound n * W, or the mask's count * W (the exact
+  // count stays on the device)
   uint32_t entries() const { return total_; }
   // device word holding the exact nonzero-digit count once ready() (nullptr for an empty plan)
-  const uint32_t* entries_dev() const { return hs_built_ ? hs_binbase_ + hs_nbins_ : nullptr; }
+  const uint32_t* entries_dev() const { return hs_built_ ? hs_binbase_ + sc_->nbins : nullptr; }
   int merge_levels() const { return merge_levels_; }
 
   // device results (read-only once ready())
@@ -177,22 +228,18 @@ class MsmPlan {
   size_t nbuckets_ = 0, max_entries_ = 0, max_tasks_ = 0, max_tasks_now_ = 0;
   int merge_levels_ = 0;
   uint32_t total_ = 0;
-  DevBuf<> vals_sorted_;  // base|sign words in bucket order (the accumulation's input)
-  DevBuf<> bstart_, bend_, cnt_, off_task_;
-  DevBuf<> lvl_all_, lvl_tsum_;  // merge level l's offsets: lvl_all_ + l * (buckets + 1)
+  // what the engines read: base|sign words in bucket order (the accumulation's input), bucket
+  // bounds, task offsets and order, merge level l's offsets (lvl_all_ + l * (buckets + 1)), and the
+  // bin bases whose last word is the entry count
+  DevBuf<> vals_sorted_;
+  DevBuf<> bstart_, bend_, off_task_;
+  DevBuf<> lvl_all_;
+  DevBuf<> perm_;  // accumulate-task order by length (longest first)
+  DevBuf<> hs_binbase_;
   bool dense_ = false;
-  // the three-pass LDS-staged bucket sort (hsort_kernels.hpp)
   bool hs_built_ = false;
-  uint32_t hs_max_tiles3_ = 0;
-  DevBuf<> hs_toff3_, hs_hist3_, hs_off3_;
-  int hs_b2_ = 0, hs_b3_ = 0, hs_k_ = 1;  // hs_k_: scalars per thread in pass A
-  uint32_t hs_nbins_ = 0, hs_nblk_ = 0, hs_max_tiles_ = 0;
-  DevBuf<> hs_hist_, hs_blkoff_, hs_binbase_;
-  DevBuf<> hs_toff_, hs_hist2_, hs_off2_, hs_subbase_;
-  DevBuf<uint2> hs_ent_a_, hs_ent_b_;  // (key, base|sign) entries
-  // accumulate-task order by length (longest first)
-  DevBuf<> perm_, tl_hist_, tl_off_;
-  DevBuf<> tsum_;  // tile sums of the look-back-free scans
+  // the three-pass LDS-staged bucket sort's memory (hsort_kernels.hpp)
+  std::shared_ptr<MsmSortScratch> sc_;
 };
 
 class MsmEngine {
