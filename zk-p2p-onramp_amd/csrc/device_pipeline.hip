@@ -90,6 +90,17 @@ int env_int(const char* name, int dflt) {
   return (v && *v) ? std::atoi(v) : dflt;
 }
 
+int env_int_range(const char* name, int dflt, int lo, int hi) {
+  const char* v = std::getenv(name);
+  if (!v || !*v) return dflt;
+  char* stop = nullptr;
+  const long x = std::strtol(v, &stop, 10);
+  if (*stop || x < lo || x > hi)
+    throw ZkpError(ZKP_ERR_INVALID_ARG, std::string(name) + ": an integer within " + std::to_string(lo) + ".." +
+                                            std::to_string(hi) + " (got '" + v + "')");
+  return (int)x;
+}
+
 MsmOptions msm_options() {
   MsmOptions o;
   const char* e = std::getenv("ZKP_MSM");
@@ -119,6 +130,11 @@ MsmOptions msm_options() {
     if (key == "sparse") {
       if (val != "0" && val != "1") throw ZkpError(ZKP_ERR_INVALID_ARG, "ZKP_MSM: sparse=0|1");
       o.sparse = val == "1" ? 1 : 0;
+      continue;
+    }
+    if (key == "share" || key == "cgate") {
+      if (val != "0" && val != "1") throw ZkpError(ZKP_ERR_INVALID_ARG, "ZKP_MSM: " + key + "=0|1");
+      (key == "share" ? o.share : o.cgate) = val == "1" ? 1 : 0;
       continue;
     }
     char* stop = nullptr;
@@ -239,6 +255,8 @@ DevicePipeline::DevicePipeline(int dev, const ZkeyParsed& z, int part, int npart
   choose_msm_params(nv, nd, opt, pw, ph);
   wsel_opt_ = opt.wsel;
   sparse_ = opt.sparse != 0;
+  share_ = opt.share != 0;
+  cgate_ = opt.cgate != 0;
   // base tables: A, B1, C, B2 indexed by witness signal (C's first nPublic+1 bases are
   // infinity, so one witness plan serves all four), H by domain index
   auto build_wtables = [&](WSet& w) {
@@ -254,6 +272,20 @@ DevicePipeline::DevicePipeline(int dev, const ZkeyParsed& z, int part, int npart
     const size_t cnt = whi_ > cfirst ? whi_ - cfirst : 0;
     fill_bases(*w.tc, cnt ? z.bf.sec[8].ptr + (cfirst - c0) * 64 : nullptr, cnt, lead, s0_);
     w.mb = std::make_shared<BaseMask>(mask_union(*w.tb1, *w.tb2, s0_));
+    // the shared build's membership table, for the plans build_engines will make: one per slot with a
+    // mask, and one for the slots without (the first of them)
+    if (sparse_ && share_) {
+      const uint32_t* bits[NPLAN] = {w.mb->data(), w.ta->present(), w.tc->present()};
+      const size_t cnt[NPLAN] = {w.mb->count, w.ta->present_count(), w.tc->present_count()};
+      bool use[NPLAN], unmasked = false;
+      int nuse = 0;
+      for (int p = 0; p < NPLAN; ++p) {
+        use[p] = bits[p] || !unmasked;
+        if (!bits[p]) unmasked = true;
+        nuse += use[p];
+      }
+      if (nuse > 1) w.memb = std::make_shared<PlanMembership>(plan_membership(bits, cnt, use, nv, s0_));
+    }
   };
   if (share) {
     if (share->dev_ != dev_ || share->wlo_ != wlo_ || share->whi_ != whi_ || share->hlo_ != hlo_ ||
@@ -263,7 +295,7 @@ DevicePipeline::DevicePipeline(int dev, const ZkeyParsed& z, int part, int npart
     for (int k = 0; k < nws_; ++k) {
       const WSet& o = share->ws_[k];
       ws_[k].pw = o.pw, ws_[k].ta = o.ta, ws_[k].tb1 = o.tb1, ws_[k].tc = o.tc, ws_[k].tb2 = o.tb2;
-      ws_[k].mb = o.mb;
+      ws_[k].mb = o.mb, ws_[k].memb = o.memb;
     }
     th_ = share->th_;
     // the H plan and engine must read th_ with the parameters it was built with: a sibling's own
@@ -358,8 +390,11 @@ void DevicePipeline::build_engines(WSet& w) {
   w.present[PL_C] = w.mask[PL_C] ? w.tc->present_count() : nv_;
   // the sort's scratch (16 of a plan's ~20 bytes per entry) once, sized for the fullest plan; every
   // plan's own outputs by its mask's count
+  // (a shared build sorts the union of the plans' signals: nearly the fullest plan's, C's, at the Venmo key)
+  const bool shared = sp && share_ && w.memb;
+  const size_t most = std::max(w.present[PL_B], std::max(w.present[PL_A], w.present[PL_C]));
   auto scratch = std::make_shared<MsmSortScratch>(
-      nv_, std::max(w.present[PL_B], std::max(w.present[PL_A], w.present[PL_C])), w.pw);
+      nv_, shared ? (w.memb->any.bits ? w.memb->any.count : nv_) : most, w.pw, shared ? (int)NPLAN : 1);
   for (int p = 0; p < NPLAN; ++p) {
     w.plan[p] = nullptr;
     for (int q = 0; q < p && !w.mask[p]; ++q)
@@ -637,10 +672,12 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
   // on the low-priority s1) then runs beside A, B1 and C instead of waiting out the H accumulation
   // and sharing the proof's tail with the H finish (+0.4 %, 7 of 8 alternated pairs:
   // profiles/g2_first_ab_r06.txt).
-  // MsmPlan::build blocks its host thread once (the sort needs the nonzero-digit
-  // count), so each stream is fed from its own host thread; the G2 thread starts
-  // once plan B is enqueued (its stream then waits on that plan's ready()), ahead of plans A and C:
-  // the G2 accumulation comes first in the proof.
+  // Nothing here blocks on the device (a plan's exact digit count stays there), but a proof enqueues
+  // a few hundred launches, so each stream is fed from its own host thread; the G2 thread starts once
+  // plan B is enqueued (its stream then waits on that plan's ready()): the G2 accumulation comes first
+  // in the proof.  With ZKP_MSM share=1 (default) ONE build fills the three plans
+  // (MsmPlan::build_shared), so all are ready before the quotient ends; share=0 builds B, A, C back
+  // to back.  cgate=1 holds C's accumulation until the quotient is done (EV_QUOT).
   // ZKP_SERIAL=1 (profiling only) chains the three streams so every kernel runs alone.
   std::exception_ptr err[3];
   std::promise<void> planned;
@@ -650,17 +687,29 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
   std::promise<void> g2acc;
   std::shared_future<void> g2acc_f = g2acc.get_future().share();
   bool g2acc_set = false;
+  const bool cgate = !serial_ && cgate_;
+  std::promise<void> quot;  // EV_QUOT recorded for this proof (cgate)
+  std::shared_future<void> quot_f = quot.get_future().share();
+  bool quot_set = false;
   auto g1_job = [&] {
     try {
       HIPX(hipSetDevice(dev_));
       HIPX(hipStreamWaitEvent(s2_, ev_[EV_H2D_END], 0));
       HIPX(hipEventRecord(ev_[EV_G1_BEGIN], s2_));
       HIPX(hipStreamWaitEvent(ws.plan[PL_B]->stream(), ev_[EV_H2D_END], 0));
-      for (int p = 0; p < NPLAN; ++p) {
-        if (ws.own[p]) ws.own[p]->build(d_wit + wlo_ * 8, whi_ - wlo_, ws.mask[p], ws.present[p]);
-        if (p == PL_B) {
-          planned.set_value();
-          planned_set = true;
+      if (sparse_ && share_ && ws.memb) {  // one build fills every plan
+        MsmPlan* own[NPLAN];
+        for (int p = 0; p < NPLAN; ++p) own[p] = ws.own[p].get();
+        MsmPlan::build_shared(own, d_wit + wlo_ * 8, whi_ - wlo_, *ws.memb);
+        planned.set_value();
+        planned_set = true;
+      } else {
+        for (int p = 0; p < NPLAN; ++p) {
+          if (ws.own[p]) ws.own[p]->build(d_wit + wlo_ * 8, whi_ - wlo_, ws.mask[p], ws.present[p]);
+          if (p == PL_B) {
+            planned.set_value();
+            planned_set = true;
+          }
         }
       }
       const MsmBases* tabs[3] = {ws.ta.get(), ws.tb1.get(), ws.tc.get()};
@@ -669,6 +718,10 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
         if (g2first && m == g2first - 1) {
           g2acc_f.get();
           HIPX(hipStreamWaitEvent(s2_, ev_[EV_G2_ACC], 0));
+        }
+        if (cgate && m == 2) {  // C fills the window of the H plan's sort
+          quot_f.get();
+          HIPX(hipStreamWaitEvent(s2_, ev_[EV_QUOT], 0));
         }
         ws.g1[m]->accumulate(*plans[m], *tabs[m]);
         HIPX(hipEventRecord(ev_[EV_ACC_A + m], s2_));
@@ -716,10 +769,13 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
       } else {
         enqueue_quotient(d_wit);
       }
+      quot.set_value();
+      quot_set = true;
       plan_h_->build(pscal_ + hlo_ * 8, hhi_ - hlo_);
       g1h_->run(*plan_h_, *th_, wh);
     } catch (...) {
       err[2] = std::current_exception();
+      if (!quot_set) quot.set_exception(std::current_exception());
     }
   };
   if (serial_) {

@@ -41,6 +41,8 @@ bool jac_to_bytes_g1(const Jac<HFq>& p, uint8_t* out);
 bool jac_to_bytes_g2(const Jac<HFq2>& p, uint8_t* out);
 
 int env_int(const char* name, int dflt);
+// the same for a knob with a range: anything but an integer within [lo, hi] is a ZKP_ERR_INVALID_ARG
+int env_int_range(const char* name, int dflt, int lo, int hi);
 
 // MSM tuning options: ONE environment variable read when a prover (or a kernel-level MSM) is built,
 // ZKP_MSM = "key=value[,key=value...]" (empty / unset: automatic everything):
@@ -58,11 +60,18 @@ int env_int(const char* name, int dflt);
 //   sparse=0|1            1 (default): a scalar whose base is the point at infinity emits no digit -- a
 //                         prover builds one witness plan per distinct mask of finite bases (B1 and B2
 //                         share one); 0: one unmasked witness plan for all four MSMs
+//   share=0|1             1 (default): a proof's witness plans come from ONE build (MsmPlan::build_shared:
+//                         the digits computed and sorted once, every entry tagged with its plans); 0: one
+//                         build per plan, back to back
+//   cgate=0|1             1: the witness accumulation C starts only when the quotient is done (it fills the
+//                         window of the H plan's sort); 0 (default): as soon as its plan is ready
 struct MsmOptions {
   int w = 0, h = 0, depth = 0, task_w = 0, task_h = 0, seg = 0, w2 = 0, wsets = 2;
   int dense = 1;
   int wsel = 0;  // 0 auto, 1 first, 2 second
   int sparse = 1;
+  int share = 1;
+  int cgate = 0;
 };
 MsmOptions msm_options();
 
@@ -285,7 +294,10 @@ class DevicePipeline {
   Stream s0_, s1_, s2_, s3_;  // first: destroyed after everything enqueued on them
   // g2first_ = k: witness accumulation k - 1 (1: the first, A) waits for EV_G2_ACC; ZKP_G2FIRST=0 lets
   // A, B1, C run beside the G2 accumulation from the start
-  int g2first_ = env_int("ZKP_G2FIRST", 1);
+  int g2first_ = env_int_range("ZKP_G2FIRST", 1, 0, 3);
+  // ZKP_MSM cgate=1: the last witness accumulation (C) waits for EV_QUOT, so it runs in the window of the
+  // H plan's sort instead of beside the quotient's NTTs; 0: as soon as its plan is ready
+  bool cgate_ = false;
   // a proof's events: the stage times of MsmOut::ms are differences of the timed ones
   enum Ev {
     EV_H2D_BEGIN,  // s0, recorded by the caller of prove_dev: the witness transfer (ms[0])
@@ -312,12 +324,15 @@ class DevicePipeline {
   // B2 (shared by the pipelines of one device), plans and engines (per pipeline).  A witness plan per
   // distinct mask of finite bases, in the order the accumulations take them: B (B2 then B1), A, C;
   // tables without a mask (and all of them under ZKP_MSM sparse=0) share one unmasked plan.  The
-  // plans build back to back on one stream and share the sort's scratch.
+  // plans share the sort's scratch on one stream: one shared build fills them all (ZKP_MSM share=1), or
+  // they build back to back (share=0).
   enum { PL_B, PL_A, PL_C, NPLAN };
   struct WSet {
     MsmParams pw;
     std::shared_ptr<MsmBases> ta, tb1, tc, tb2;
     std::shared_ptr<BaseMask> mb;
+    // which plans each signal belongs to and the signals of any (ZKP_MSM share=1 with more than one plan)
+    std::shared_ptr<PlanMembership> memb;
     std::unique_ptr<MsmPlan> own[NPLAN];  // own[p]: built for slot p (null: slot p uses an earlier one)
     MsmPlan* plan[NPLAN] = {};            // the plan each slot takes
     const uint32_t* mask[NPLAN] = {};  // each slot's index list of finite bases (null: no mask)
@@ -332,6 +347,7 @@ class DevicePipeline {
   WSet ws_[2];
   int nws_ = 1, wsel_opt_ = 0;
   bool sparse_ = true;         // ZKP_MSM sparse=
+  bool share_ = true;          // ZKP_MSM share=
   bool wset2_tables_ = false;  // this device holds the second configuration's tables (add_second_wset)
   size_t nv_ = 0;              // witness signals of this pipeline's slice
   void build_engines(WSet& w);

@@ -26,6 +26,9 @@
 //        scatter straight to global memory instead)
 // Order inside a bucket is not fixed (LDS atomics); a bucket sum is the same group element in
 // any order, so the MSM result does not change.
+// A shared build of several plans over one scalar vector (MsmPlan::build_shared) runs A and B once
+// with the plans' tag in every entry's key word (k_hs_scatter1<K, MASK, true>) and the tiled pass C
+// per (plan, sub-bin, bucket, tile): k_hs_count3 / one scan / k_hs_scatter3 / k_hs_bounds3p per plan.
 // Included by msm.hip inside namespace zkp's anonymous namespace (needs msm_kernels.hpp).
 #pragma once
 
@@ -36,6 +39,11 @@ constexpr int HS_CAP = 8192;        // pass-C sub-bins up to this many entries s
 constexpr int HS_FINE_TPB = 512;
 constexpr int HS_MAX_B1 = 9, HS_MAX_B2 = 9, HS_B3 = 5;
 constexpr int SC_TPB = 1024;        // look-back-free scan
+// the shared build of up to HS_NPLAN plans over one scalar vector (k_hs_scatter1<K, MASK, true>): the bucket
+// key takes at most 27 bits, so the top bits of an entry's .x word carry which plans the entry
+// belongs to (bit HS_TAG_SHIFT + p: plan p); .y (31-bit base index and the sign) has no bit to spare
+constexpr int HS_NPLAN = 3, HS_TAG_SHIFT = 29;
+constexpr uint32_t HS_KEY_MASK = (1u << HS_TAG_SHIFT) - 1;
 constexpr int SC_TILE = SC_TPB * 4;
 
 // exclusive scan of one value per thread over a workgroup of NT threads (NT % 64 == 0)
@@ -251,12 +259,19 @@ __global__ __launch_bounds__(512) void k_hs_binbase(const uint32_t* __restrict__
 
 // the block's digits counted per bin, scanned, placed in an LDS stage grouped by bin (LDS
 // atomics), then the stage written out linearly: consecutive lanes, consecutive addresses of a run
-template <int K, bool MASK>
+// TAG (the shared build): memb[i] = the plans scalar i belongs to rides in the key word's top bits, so
+// the bin is taken from the key bits alone; without TAG `memb` is never read
+template <bool TAG>
+__device__ __forceinline__ uint32_t hs_bin(uint32_t x, int sh1) {
+  return TAG ? (x & HS_KEY_MASK) >> sh1 : x >> sh1;
+}
+template <int K, bool MASK, bool TAG = false>
 __global__ __launch_bounds__(HS_TPB) void k_hs_scatter1(const uint32_t* __restrict__ scalars, uint32_t n,
                                                         const uint32_t* __restrict__ index, uint32_t m, int c, int W,
                                                         int T, int sh1, uint32_t nbins,
                                                         const uint32_t* __restrict__ pos,
-                                                        uint2* __restrict__ ent) {
+                                                        uint2* __restrict__ ent,
+                                                        const uint8_t* __restrict__ memb = nullptr) {
   constexpr int NB = 1 << HS_MAX_B1;
   // dynamic LDS: the stage (K * HS_TPB * W entries) then cnt / off (nbins each): 54.3 KiB for the
   // H plan (W = 13, K = 2, 2^7 bins) -> three workgroups per CU
@@ -277,6 +292,7 @@ __global__ __launch_bounds__(HS_TPB) void k_hs_scatter1(const uint32_t* __restri
     const bool act = j < m;
     const uint32_t i = act && MASK ? index[j] : j;
     if (act) msmk::load_scalar(scalars, i, s);
+    const uint32_t tag = TAG && act ? (uint32_t)memb[i] << HS_TAG_SHIFT : 0u;
     uint32_t carry = 0;
 #pragma unroll
     for (int w = 0; w < EM; ++w) {
@@ -284,7 +300,7 @@ __global__ __launch_bounds__(HS_TPB) void k_hs_scatter1(const uint32_t* __restri
       if (w < W) {
         uint32_t key, val;
         if (msmk::digit_entry(s, w, c, T, n, i, carry, key, val) && act) {
-          e[q][w] = make_uint2(key, val);
+          e[q][w] = make_uint2(key | tag, val);  // (never NONE: key < 2^27)
           atomicAdd(&cnt[key >> sh1], 1u);
         }
       }
@@ -300,14 +316,14 @@ __global__ __launch_bounds__(HS_TPB) void k_hs_scatter1(const uint32_t* __restri
   for (int q = 0; q < K; ++q)
 #pragma unroll
     for (int w = 0; w < EM; ++w)
-      if (e[q][w].x != NONE) stage[atomicAdd(&cnt[e[q][w].x >> sh1], 1u)] = e[q][w];
+      if (e[q][w].x != NONE) stage[atomicAdd(&cnt[hs_bin<TAG>(e[q][w].x, sh1)], 1u)] = e[q][w];
   __syncthreads();
   for (uint32_t b = threadIdx.x; b < nbins; b += HS_TPB)  // the cursors become destination bases
     off[b] = pos[(size_t)b * gridDim.x + blockIdx.x] - off[b];
   __syncthreads();
   for (uint32_t j = threadIdx.x; j < total; j += HS_TPB) {
     const uint2 e = stage[j];
-    ent[off[e.x >> sh1] + j] = e;
+    ent[off[hs_bin<TAG>(e.x, sh1)] + j] = e;
   }
 }
 
@@ -476,6 +492,121 @@ __global__ __launch_bounds__(HS_TPB) void k_hs_bounds3(const uint32_t* __restric
     s = off3[base + (size_t)f * nt];
     e = f + 1 < nf ? off3[base + (size_t)(f + 1) * nt] : subbase[q + 1];
   }
+  start[k] = s;
+  end[k] = e;
+  cnt[k] = (e - s + S - 1) / S;
+}
+
+// ---------------------------------------------------------------- pass C, tiled, for tagged entries
+// The shared build's pass C: one pass over the sub-bin-sorted entries of the union of up to HS_NPLAN
+// plans fills every plan's bucket-ordered base|sign words.  Counts per (plan, sub-bin, bucket, tile):
+// plan p's flat array (laid out as the tiled variant's, `stride` words apart) holds the entries whose
+// tag has bit p.  ONE exclusive scan runs over the concatenation, so plan p's positions are its
+// scanned words minus its first one (off3[p * stride]: the entries of the plans before it).  A
+// plan's array is scanned one word past its last tile (stride > tiles * nf), and the tiles past the
+// used ones count nothing: the word at toff3[q + 1] * nf is where sub-bin q's entries end, the one at
+// toff3[nq] * nf the plan's entry count.
+__global__ __launch_bounds__(HS_TPB) void k_hs_count3(const uint2* __restrict__ ent,
+                                                      const uint32_t* __restrict__ subbase,
+                                                      const uint32_t* __restrict__ toff3, uint32_t nq, uint32_t nf,
+                                                      uint32_t pmask, size_t stride, uint32_t* __restrict__ hist3) {
+  __shared__ uint32_t h[HS_NPLAN << HS_MAX_B2];
+  HsTile r;
+  if (!hs_tile(subbase, toff3, nq, blockIdx.x, r)) return;
+  for (uint32_t s = threadIdx.x; s < HS_NPLAN * nf; s += HS_TPB) h[s] = 0;
+  __syncthreads();
+  for (uint32_t j0 = r.lo; j0 < r.hi; j0 += HS_TPB) {  // whole waves iterate (lds_claim ballots)
+    const uint32_t j = j0 + threadIdx.x;
+    const bool ok = j < r.hi;
+    const uint32_t x = ok ? ent[j].x : 0u;
+#pragma unroll
+    for (int p = 0; p < HS_NPLAN; ++p)
+      if (pmask >> p & 1) (void)lds_claim(h + p * nf, x & (nf - 1), (x >> (HS_TAG_SHIFT + p)) & 1);
+  }
+  __syncthreads();
+  const size_t base = (size_t)toff3[r.b] * nf + r.t;
+#pragma unroll
+  for (int p = 0; p < HS_NPLAN; ++p)
+    if (pmask >> p & 1)
+      for (uint32_t s = threadIdx.x; s < nf; s += HS_TPB) hist3[p * stride + base + (size_t)s * r.nt] = h[p * nf + s];
+}
+
+struct HsPlanOut {
+  uint32_t* v[HS_NPLAN];
+};
+// a tile read once, then staged in LDS and written as bucket runs of base|sign words once per plan
+// the entries belong to
+__global__ __launch_bounds__(HS_TPB) void k_hs_scatter3(const uint2* __restrict__ ent,
+                                                        const uint32_t* __restrict__ subbase,
+                                                        const uint32_t* __restrict__ toff3, uint32_t nq, uint32_t nf,
+                                                        uint32_t pmask, size_t stride,
+                                                        const uint32_t* __restrict__ off3, HsPlanOut out) {
+  constexpr int NS = 1 << HS_MAX_B2;
+  __shared__ uint32_t cnt[NS], off[NS], gbase[NS];
+  __shared__ uint2 stage[HS_TILE];
+  __shared__ uint32_t sh[HS_TPB / 64];
+  HsTile r;
+  if (!hs_tile(subbase, toff3, nq, blockIdx.x, r)) return;
+  constexpr int PT = HS_TILE / HS_TPB;
+  uint2 e[PT];
+#pragma unroll
+  for (int p = 0; p < PT; ++p) {
+    const uint32_t j = r.lo + p * HS_TPB + threadIdx.x;
+    e[p] = j < r.hi ? ent[j] : make_uint2(0u, 0u);  // (no tag: in no plan)
+  }
+  const size_t base = (size_t)toff3[r.b] * nf + r.t;
+#pragma unroll
+  for (int pl = 0; pl < HS_NPLAN; ++pl) {
+    if (!(pmask >> pl & 1)) continue;
+    for (uint32_t s = threadIdx.x; s < nf; s += HS_TPB) cnt[s] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < PT; ++p) (void)lds_claim(cnt, e[p].x & (nf - 1), (e[p].x >> (HS_TAG_SHIFT + pl)) & 1);
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < nf; s += HS_TPB) off[s] = cnt[s];
+    __syncthreads();
+    const uint32_t total = lds_excl_scan<HS_TPB, NS / HS_TPB>(off, nf, sh);
+    const uint32_t* o3 = off3 + pl * stride;
+    const uint32_t pbase = o3[0];
+    for (uint32_t s = threadIdx.x; s < nf; s += HS_TPB) {
+      cnt[s] = off[s];  // cursors
+      gbase[s] = o3[base + (size_t)s * r.nt] - pbase - off[s];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < PT; ++p) {
+      const bool in = (e[p].x >> (HS_TAG_SHIFT + pl)) & 1;
+      const uint32_t slot = lds_claim(cnt, e[p].x & (nf - 1), in);
+      if (in) stage[slot] = e[p];
+    }
+    __syncthreads();
+    uint32_t* __restrict__ vout = out.v[pl];
+    for (uint32_t j = threadIdx.x; j < total; j += HS_TPB) {
+      const uint2 x = stage[j];
+      vout[gbase[x.x & (nf - 1)] + j] = x.y;
+    }
+    __syncthreads();
+  }
+}
+// k_hs_bounds3 for one plan of the shared build (off3: the plan's scanned array, see k_hs_count3);
+// *count = the plan's entries
+__global__ __launch_bounds__(HS_TPB) void k_hs_bounds3p(const uint32_t* __restrict__ toff3,
+                                                        const uint32_t* __restrict__ off3, uint32_t nq, int b3,
+                                                        uint32_t nb, uint32_t S, uint32_t* __restrict__ start,
+                                                        uint32_t* __restrict__ end, uint32_t* __restrict__ cnt,
+                                                        uint32_t* __restrict__ count) {
+  const uint32_t k = blockIdx.x * HS_TPB + threadIdx.x;
+  if (k > nb) return;
+  const uint32_t nf = 1u << b3, pbase = off3[0];
+  if (k == nb) {
+    cnt[nb] = 0;
+    *count = off3[(size_t)toff3[nq] * nf] - pbase;
+    return;
+  }
+  const uint32_t q = k >> b3, f = k & (nf - 1);
+  const uint32_t nt = toff3[q + 1] - toff3[q];
+  const size_t base = (size_t)toff3[q] * nf;
+  const uint32_t s = off3[base + (size_t)f * nt] - pbase, e = off3[base + (size_t)(f + 1) * nt] - pbase;
   start[k] = s;
   end[k] = e;
   cnt[k] = (e - s + S - 1) / S;

@@ -60,6 +60,31 @@ __global__ __launch_bounds__(TPB) void k_mask_or(const uint32_t* __restrict__ a,
   out[j] = v;
   if (v) atomicAdd(count, (uint32_t)__popc(v));
 }
+// PlanMembership: memb[i] = bit p when plan p is used and scalar i is in its mask (no mask: every one);
+// a wave's ballot gives two words of the mask of the scalars with any bit, count += those
+struct MembBits {
+  const uint32_t* bits[PlanMembership::NPLAN];
+  uint32_t all;  // plans without a mask (every scalar belongs)
+  uint32_t use;
+};
+__global__ __launch_bounds__(TPB) void k_membership(MembBits in, uint32_t n, uint8_t* __restrict__ memb,
+                                                    uint32_t* __restrict__ any, uint32_t* __restrict__ count) {
+  const uint32_t i = blockIdx.x * TPB + threadIdx.x;
+  uint32_t tag = 0;
+  if (i < n) {
+#pragma unroll
+    for (int p = 0; p < PlanMembership::NPLAN; ++p) {
+      if (!(in.use >> p & 1)) continue;
+      const uint32_t bit = (in.all >> p & 1) ? 1u : (in.bits[p][i >> 5] >> (i & 31)) & 1u;
+      tag |= bit << p;
+    }
+    memb[i] = (uint8_t)tag;
+  }
+  const uint64_t m = __ballot(tag != 0);
+  const uint32_t lane = threadIdx.x & 63;
+  if ((lane & 31) == 0 && i < n) any[i >> 5] = (uint32_t)(m >> lane);
+  if (lane == 0 && m) atomicAdd(count, (uint32_t)__popcll(m));
+}
 
 // G2 (Fq2) accumulation and bucket merges (the wide finish kernels): without a bound the
 // compiler takes 256 VGPRs + AGPRs (one wave per SIMD, nothing to hide the mad-chain
@@ -312,10 +337,37 @@ BaseMask mask_union(const MsmBases& a, const MsmBases& b, hipStream_t st) {
   return m;
 }
 
+PlanMembership plan_membership(const uint32_t* const bits[PlanMembership::NPLAN],
+                               const size_t count[PlanMembership::NPLAN], const bool use[PlanMembership::NPLAN],
+                               size_t n, hipStream_t st) {
+  PlanMembership r;
+  r.any.count = n;
+  MembBits in{};
+  for (int p = 0; p < PlanMembership::NPLAN; ++p) {
+    if (!use[p]) continue;
+    in.use |= 1u << p;
+    in.bits[p] = bits[p];
+    if (!bits[p]) in.all |= 1u << p;
+    r.count[p] = bits[p] ? count[p] : n;
+  }
+  if (n == 0) {
+    r.any.count = 0;
+    return r;
+  }
+  r.memb = DevBuf<uint8_t>(n);
+  r.any.bits = DevBuf<>((n + 31) / 32);
+  DevBuf<> cnt(1);
+  HIPX(hipMemsetAsync(cnt, 0, 4, st));
+  hipLaunchKernelGGL(k_membership, dim3(grid_for(n)), dim3(TPB), 0, st, in, (uint32_t)n, r.memb, r.any.bits, cnt);
+  settle_mask(r.any, cnt, n, st);
+  return r;
+}
+
 // ------------------------------------------------------------------ MsmPlan
 
-MsmSortScratch::MsmSortScratch(size_t max_n_, size_t max_present, const MsmParams& prm_)
-    : prm(prm_), max_n(std::max<size_t>(max_n_, 1)) {
+MsmSortScratch::MsmSortScratch(size_t max_n_, size_t max_present, const MsmParams& prm_, int nplans_)
+    : prm(prm_), nplans(nplans_), max_n(std::max<size_t>(max_n_, 1)) {
+  if (nplans < 1 || nplans > PlanMembership::NPLAN) throw std::invalid_argument("MSM: plans of a shared build");
   if (prm.c < MsmParams::MIN_C || prm.c > MsmParams::MAX_C || prm.windows > HS_STAGE / HS_TPB)
     throw std::invalid_argument("MSM: window bits outside the plan's range");
   if (max_n * prm.depth >= (size_t(1) << 31)) throw std::runtime_error("MSM size too large for 31-bit base indices");
@@ -348,8 +400,13 @@ MsmSortScratch::MsmSortScratch(size_t max_n_, size_t max_present, const MsmParam
   const uint32_t max_tiles3 = (uint32_t)((max_entries + HS_TILE - 1) / HS_TILE + nq);
   const size_t nh3 = ((size_t)max_tiles3 << b3) + 1;
   toff3 = DevBuf<>((size_t)nq + 1);
-  hist3 = DevBuf<>(nh3);
-  off3 = DevBuf<>(nh3);
+  // a shared build keeps HS_NPLAN count arrays, stride3 apart, whether or not every plan is there
+  stride3 = nh3;
+  const size_t nh3_all = nplans > 1 ? nh3 * HS_NPLAN : nh3;
+  if (nh3_all >= 0xffffffffull) throw std::runtime_error("MSM size too large for the sort's scans");
+  hist3 = DevBuf<>(nh3_all);
+  off3 = DevBuf<>(nh3_all);
+  if (nplans > 1) binbase = DevBuf<>(nbins + 1);
   const size_t nh = (size_t)nbins * nblk, nh2 = (size_t)max_tiles << b2;
   hist = DevBuf<>(nh);
   blkoff = DevBuf<>(nh);
@@ -359,7 +416,7 @@ MsmSortScratch::MsmSortScratch(size_t max_n_, size_t max_present, const MsmParam
   subbase = DevBuf<>((size_t)nq + 1);
   ent_a = DevBuf<uint2>(max_entries);
   ent_b = DevBuf<uint2>(max_entries);
-  const size_t scan_n = std::max(std::max(std::max(nbuckets + 1, nh3), std::max(nh2, ntl)), nh);
+  const size_t scan_n = std::max(std::max(std::max(nbuckets + 1, nh3_all), std::max(nh2, ntl)), nh);
   tsum = DevBuf<>(scan_tiles_for(scan_n) + 1);
 }
 
@@ -395,6 +452,11 @@ static auto hs_scatter1_for(int k) {
   return k == 4 ? k_hs_scatter1<4, MASK> : (k == 2 ? k_hs_scatter1<2, MASK> : k_hs_scatter1<1, MASK>);
 }
 
+template <bool MASK>
+static auto hs_scatter1_tagged_for(int k) {
+  return k == 4 ? k_hs_scatter1<4, MASK, true> : (k == 2 ? k_hs_scatter1<2, MASK, true> : k_hs_scatter1<1, MASK, true>);
+}
+
 void MsmPlan::build(const uint32_t* scalars, size_t n, const uint32_t* present, size_t n_present) {
   if (n > max_n_) throw std::runtime_error("MSM: n exceeds plan capacity");
   if (!present) n_present = n;
@@ -412,11 +474,7 @@ void MsmPlan::build(const uint32_t* scalars, size_t n, const uint32_t* present, 
   // (entries_dev)
   total_ = (uint32_t)(n_present * W);
   hs_built_ = false;
-  if (total_ == 0) {
-    HIPX(hipMemsetAsync(bstart_, 0, (nbuckets_ + 1) * 4, st));
-    HIPX(hipMemsetAsync(bend_, 0, (nbuckets_ + 1) * 4, st));
-    HIPX(hipMemsetAsync(sc.cnt, 0, (nbuckets_ + 1) * 4, st));
-  } else {
+  if (total_ != 0) {
     // the hand-written three-pass LDS-staged bucket sort (hsort_kernels.hpp), zero digits and the
     // scalars whose base is at infinity dropped in pass A (it visits only the mask's index list).  Dense plans (uniform scalars: the H MSM) group their sub-bins with one workgroup each
     // (k_hs_fine); compacted plans (the witness: whole waves of one bin / sub-bin / bucket) take the
@@ -438,7 +496,8 @@ void MsmPlan::build(const uint32_t* scalars, size_t n, const uint32_t* present, 
     auto scatter1 = present ? hs_scatter1_for<true>(k) : hs_scatter1_for<false>(k);
     const size_t lds1 = (size_t)k * HS_TPB * W * 8 + (size_t)hs_nbins_ * 8;
     hipLaunchKernelGGL(scatter1, dim3(nblk), dim3(HS_TPB), lds1, st, scalars, (uint32_t)n, present,
-                       (uint32_t)n_present, prm_.c, (int)W, prm_.depth, sh1, hs_nbins_, sc.blkoff, ea);
+                       (uint32_t)n_present, prm_.c, (int)W, prm_.depth, sh1, hs_nbins_, sc.blkoff, ea,
+                       (const uint8_t*)nullptr);
     // B: bins -> sub-bins (tiles past the used ones exit; their counters stay zero)
     const size_t tiles = ((size_t)total_ + HS_TILE - 1) / HS_TILE + hs_nbins_;
     const size_t nh2 = tiles << hs_b2_;
@@ -471,6 +530,18 @@ void MsmPlan::build(const uint32_t* scalars, size_t n, const uint32_t* present, 
     }
     hs_built_ = true;
   }
+  build_tail(total_ == 0);
+}
+
+void MsmPlan::build_tail(bool empty) {
+  MsmSortScratch& sc = *sc_;
+  hipStream_t st = stream_;
+  const uint32_t nb = (uint32_t)nbuckets_;
+  if (empty) {
+    HIPX(hipMemsetAsync(bstart_, 0, (nbuckets_ + 1) * 4, st));
+    HIPX(hipMemsetAsync(bend_, 0, (nbuckets_ + 1) * 4, st));
+    HIPX(hipMemsetAsync(sc.cnt, 0, (nbuckets_ + 1) * 4, st));
+  }
   // accumulate-task offsets and the heavy-bucket merge levels' offsets (look-back-free scans: they
   // run beside the accumulations of the other streams)
   scan_nolookback(sc.cnt, off_task_, nbuckets_ + 1, sc.tsum, st);
@@ -495,6 +566,90 @@ void MsmPlan::build(const uint32_t* scalars, size_t n, const uint32_t* present, 
   }
   HIPX(hipGetLastError());
   HIPX(hipEventRecord(ready_, st));
+}
+
+void MsmPlan::build_shared(MsmPlan* const plans[PlanMembership::NPLAN], const uint32_t* scalars, size_t n,
+                           const PlanMembership& mem) {
+  static_assert(PlanMembership::NPLAN == HS_NPLAN, "the tag bits of the sort's entries");
+  MsmPlan* first = nullptr;
+  uint32_t pmask = 0;
+  for (int p = 0; p < HS_NPLAN; ++p) {
+    MsmPlan* pl = plans[p];
+    if (!pl) continue;
+    if (!first) first = pl;
+    if (pl->sc_ != first->sc_ || pl->stream_ != first->stream_ || pl->dense_)
+      throw std::runtime_error("MSM: a shared build takes compacted plans of one scratch and one stream");
+    if (n > pl->max_n_) throw std::runtime_error("MSM: n exceeds plan capacity");
+    if (mem.count[p] > n || mem.count[p] * pl->prm_.windows > pl->max_entries_)
+      throw std::runtime_error("MSM: finite bases exceed plan capacity");
+    pl->n_ = n;
+    pl->total_ = (uint32_t)(mem.count[p] * pl->prm_.windows);
+    pl->hs_built_ = false;
+    if (pl->total_) pmask |= 1u << p;
+  }
+  if (!first) return;
+  MsmSortScratch& sc = *first->sc_;
+  const MsmParams& prm = first->prm_;
+  const uint32_t* index = mem.any.list();
+  const size_t n_any = mem.any.bits ? mem.any.count : n;
+  if (sc.nplans < 2 || n_any > n || n_any * prm.windows > sc.max_entries)
+    throw std::runtime_error("MSM: sort scratch not built for this shared build");
+  hipStream_t st = first->stream_;
+  if (pmask) {
+    // passes A and B as in build(), over the union of the plans' scalars and with the plans' tag in
+    // every entry; pass C (tiled) per plan
+    const uint32_t W = (uint32_t)prm.windows, nb = (uint32_t)first->nbuckets_;
+    const int b2 = sc.b2, b3 = sc.b3, k = sc.k, sh1 = b2 + b3;
+    const uint32_t nbins = sc.nbins, nsub = 1u << b2, nf = 1u << b3;
+    const uint32_t total = (uint32_t)(n_any * W);
+    const uint32_t nblk = (uint32_t)((n_any + k * HS_TPB - 1) / (k * HS_TPB));
+    uint2* ea = sc.ent_a;
+    uint2* eb = sc.ent_b;
+    auto count1 = index ? hs_count1_for<true>(k) : hs_count1_for<false>(k);
+    hipLaunchKernelGGL(count1, dim3(nblk), dim3(HS_TPB), 0, st, scalars, (uint32_t)n, index, (uint32_t)n_any, prm.c,
+                       (int)W, prm.depth, sh1, nbins, sc.hist);
+    scan_nolookback(sc.hist, sc.blkoff, (size_t)nbins * nblk, sc.tsum, st);
+    hipLaunchKernelGGL(k_hs_binbase, dim3(1), dim3(512), 0, st, sc.blkoff, sc.hist, nbins, nblk, sc.binbase, sc.toff);
+    auto scatter1 = index ? hs_scatter1_tagged_for<true>(k) : hs_scatter1_tagged_for<false>(k);
+    const size_t lds1 = (size_t)k * HS_TPB * W * 8 + (size_t)nbins * 8;
+    hipLaunchKernelGGL(scatter1, dim3(nblk), dim3(HS_TPB), lds1, st, scalars, (uint32_t)n, index, (uint32_t)n_any,
+                       prm.c, (int)W, prm.depth, sh1, nbins, sc.blkoff, ea, mem.memb.get());
+    const size_t tiles = ((size_t)total + HS_TILE - 1) / HS_TILE + nbins;
+    const size_t nh2 = tiles << b2;
+    HIPX(hipMemsetAsync(sc.hist2, 0, nh2 * 4, st));
+    hipLaunchKernelGGL(k_hs_count2<true>, dim3((unsigned)tiles), dim3(HS_TPB), 0, st, ea, sc.binbase, sc.toff, nbins, b3,
+                       nsub, sc.hist2);
+    scan_nolookback(sc.hist2, sc.off2, nh2, sc.tsum, st);
+    const uint32_t nq = nbins * nsub;
+    hipLaunchKernelGGL(k_hs_subbase, dim3(grid_for(nq + 1)), dim3(HS_TPB), 0, st, sc.off2, sc.binbase, sc.toff, nbins,
+                       nsub, sc.subbase);
+    hipLaunchKernelGGL((k_hs_scatter2<true, false>), dim3((unsigned)tiles), dim3(HS_TPB), 0, st, ea, sc.binbase, sc.toff,
+                       nbins, b3, nsub, sc.off2, eb, nullptr);
+    hipLaunchKernelGGL(k_hs_subtiles, dim3(1), dim3(SC_TPB), 0, st, sc.subbase, nq, sc.toff3);
+    // every plan's array: its tiles' counts and one word more (k_hs_count3), all scanned as one
+    const size_t tiles3 = ((size_t)total + HS_TILE - 1) / HS_TILE + nq, stride = (tiles3 << b3) + 1;
+    if (stride > sc.stride3) throw std::runtime_error("MSM: sort scratch too small for this shared build");
+    HIPX(hipMemsetAsync(sc.hist3, 0, stride * HS_NPLAN * 4, st));
+    hipLaunchKernelGGL(k_hs_count3, dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, sc.subbase, sc.toff3, nq, nf, pmask,
+                       stride, sc.hist3);
+    scan_nolookback(sc.hist3, sc.off3, stride * HS_NPLAN, sc.tsum, st);
+    HsPlanOut out{};
+    for (int p = 0; p < HS_NPLAN; ++p)
+      if (pmask >> p & 1) out.v[p] = plans[p]->vals_sorted_;
+    hipLaunchKernelGGL(k_hs_scatter3, dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, sc.subbase, sc.toff3, nq, nf, pmask,
+                       stride, sc.off3, out);
+    for (int p = 0; p < HS_NPLAN; ++p) {
+      if (!(pmask >> p & 1)) continue;
+      MsmPlan& pl = *plans[p];
+      hipLaunchKernelGGL(k_hs_bounds3p, dim3(grid_for((size_t)nb + 1)), dim3(HS_TPB), 0, st, sc.toff3,
+                         sc.off3 + p * stride, nq, b3, nb, (uint32_t)prm.S, pl.bstart_, pl.bend_, sc.cnt,
+                         pl.hs_binbase_ + nbins);
+      pl.hs_built_ = true;
+      pl.build_tail(false);
+    }
+  }
+  for (int p = 0; p < HS_NPLAN; ++p)
+    if (plans[p] && !(pmask >> p & 1)) plans[p]->build_tail(true);
 }
 
 // ------------------------------------------------------------------ MsmEngine

@@ -21,6 +21,8 @@
 //     3. bounds : bucket [start, end) ranges, accumulate-task offsets (tasks of
 //                 <= S entries never straddle a bucket), the task order by length and
 //                 the offsets of the heavy-bucket merge levels.
+//     Plans over the same scalars that differ only in their masks (a proof's witness plans B, A, C)
+//     come from one build_shared: steps 1 and 2 once over the union, the entries tagged by plan.
 //
 //  MsmEngine (per curve and stream: partial sums, buckets, reduction tree)
 //     4. accumulate: one thread per task, mixed XYZZ additions of gathered bases;
@@ -162,13 +164,33 @@ class MsmBases {
 // zkey's B1 and B2); no mask when either table has none.  Waits for the stream once.
 BaseMask mask_union(const MsmBases& a, const MsmBases& b, hipStream_t st);
 
+// Which of up to NPLAN plans over the same n scalars each scalar belongs to (MsmPlan::build_shared):
+// memb[i] has bit p set when scalar i's base is finite in plan p's mask; `any` masks the scalars with
+// at least one bit (its index list is what the shared pass A visits; no mask when that is all of them).
+struct PlanMembership {
+  static constexpr int NPLAN = 3;
+  DevBuf<uint8_t> memb;
+  BaseMask any;
+  size_t count[NPLAN] = {};  // scalars with bit p
+  size_t bytes() const { return memb.count() + (any.bits.count() + any.index.count()) * 4; }
+};
+// bits[p]: plan p's mask over n scalars (BaseMask::data; null: every scalar belongs) with count[p] set
+// bits; use[p] false: no plan p (its bit stays clear).  Built on the device; waits for the stream once.
+PlanMembership plan_membership(const uint32_t* const bits[PlanMembership::NPLAN],
+                               const size_t count[PlanMembership::NPLAN], const bool use[PlanMembership::NPLAN],
+                               size_t n, hipStream_t st);
+
 // The bucket sort's working memory and geometry: entries, histograms, tile offsets and scan sums,
 // 16 of a plan's ~20 bytes per entry.  Nothing reads it once MsmPlan::build has enqueued its last
 // kernel, so plans with the same parameters that build back to back on ONE stream share one.
 struct MsmSortScratch {
-  // max_n scalars of which at most max_present emit digits
-  MsmSortScratch(size_t max_n, size_t max_present, const MsmParams& prm);
+  // max_n scalars of which at most max_present emit digits; nplans > 1: the scratch of a shared build
+  // (MsmPlan::build_shared) of so many plans, whose pass C keeps its counts per plan
+  MsmSortScratch(size_t max_n, size_t max_present, const MsmParams& prm, int nplans = 1);
   MsmParams prm;
+  int nplans = 1;
+  size_t stride3 = 0;  // words between the plans' pass-C count arrays
+  DevBuf<> binbase;    // a shared build's bin bases (one plan's live in the plan: the entry count)
   size_t max_n, max_entries, max_tasks, nbuckets;
   int merge_levels = 0;
   int b2 = 0, b3 = 0, k = 1;  // sub-bin / bucket bits of the key, scalars per thread in pass A
@@ -193,6 +215,14 @@ class MsmPlan {
   // Enqueues on the plan's stream, never blocks the host (the exact entry count stays on the
   // device: entries_dev()); records ready() at the end.
   void build(const uint32_t* scalars, size_t n, const uint32_t* present = nullptr, size_t n_present = 0);
+  // One build for up to PlanMembership::NPLAN compacted plans over the same scalars (null: no plan p)
+  // that share one scratch (made for so many plans) and one stream: the digits are computed and
+  // sorted once over the scalars of mem.any, every entry tagged with the plans it belongs to; the
+  // last pass writes each plan's bucket-ordered words.  Every plan ends as build() with its own mask
+  // would leave it (the same outputs, the exact entry count; order inside a bucket is unspecified in
+  // both) and records its ready(): the plans with entries in the order of the array, then the empty ones.
+  static void build_shared(MsmPlan* const plans[PlanMembership::NPLAN], const uint32_t* scalars, size_t n,
+                           const PlanMembership& mem);
   // dense (uniform scalars, e.g. the H MSM's: nearly every digit is nonzero and the buckets evenly
   // filled): pass C of the sort takes one workgroup per sub-bin; otherwise (the 0/1-heavy witness:
   // whole waves of entries in one bucket) wave-aggregated LDS claims and a tiled pass C
@@ -221,6 +251,9 @@ class MsmPlan {
   size_t max_tasks() const { return max_tasks_; }
 
  private:
+  // what follows the sort: an empty plan's bounds (empty) or the task offsets, the task order and the
+  // merge levels' offsets from the bucket bounds and task counts; records ready()
+  void build_tail(bool empty);
   MsmParams prm_;
   size_t max_n_, n_ = 0;
   hipStream_t stream_;
