@@ -69,15 +69,33 @@ static host::Jac<HF> run(std::vector<uint32_t>& pts, std::vector<uint32_t>& sc, 
   std::vector<uint32_t> buckets((size_t)nb * 4 * FW);
   for (uint32_t b = 0; b < nb; ++b)
     msmk::merge_final<F>(b, part.data(), part1.data(), off.data(), nb, prm.S2, levels, buckets.data());
-  // reduction (as run_finish): segments, then the K subset sums, each by one subset_first thread whose
-  // fan-in covers all its values (the device sums them by LDS trees: the same group elements)
-  const uint32_t M = prm.M, lgP = prm.lgP(), K = prm.K(), P = half / M, fan = std::max<uint32_t>(P, 1);
-  std::vector<uint32_t> ss((size_t)G * P * 4 * FW), tt(ss.size());
-  for (uint32_t id = 0; id < G * P; ++id) msmk::reduce_segments<F>(id, buckets.data(), G, half, M, ss.data(), tt.data());
+  // reduction, first level (as run_finish): the row and column partials by rowcol_chain with the engine's
+  // chain lengths, then every sum from its partials in order (the device adds them by a shuffle
+  // butterfly, rowcol_tree: the same group element), placed by rowcol_slot
+  const uint32_t U = prm.U(), V = prm.V(), G2 = prm.subgroups();
+  const msmk::RowCol rc = msmk::rowcol_make(G, U, V, msmk::ROWCOL_CHAIN, msmk::ROWCOL_SPAN);
+  const uint32_t nparts = rc.row_parts() + rc.col_parts();
+  std::vector<uint32_t> rpart((size_t)nparts * 4 * FW, 0xdeadbeefu), xs((size_t)G2 * V * 4 * FW, 0xdeadbeefu);
+  for (uint32_t id = 0; id < nparts; ++id) msmk::rowcol_chain<F>(id, buckets.data(), rc, rpart.data(), xs.data());
+  for (uint32_t seg = 0; seg < G * (U + V); ++seg) {
+    const uint32_t slot = msmk::rowcol_slot(seg, rc);
+    if (slot == msmk::ROWCOL_NONE) continue;
+    const bool col = seg >= G * U;
+    const uint32_t n = col ? rc.nc() : rc.nr();
+    const size_t p0 = col ? (size_t)rc.row_parts() + (size_t)(seg - G * U) * n : (size_t)seg * n;
+    auto v = load_xyzz<F>(rpart.data(), p0);
+    for (uint32_t q = 1; q < n; ++q) xyzz_add(v, load_xyzz<F>(rpart.data(), p0 + q));
+    store_xyzz(xs.data(), slot, v);
+  }
+  // second level over the 2G sub-groups of V points: segments, then the K subset sums, each by one
+  // subset_first thread whose fan-in covers all its values (the device sums them by LDS trees)
+  const uint32_t M = prm.M, lgP = prm.lgP(), K = prm.K(), P = V / M, fan = std::max<uint32_t>(P, 1);
+  std::vector<uint32_t> ss((size_t)G2 * P * 4 * FW), tt(ss.size());
+  for (uint32_t id = 0; id < G2 * P; ++id) msmk::reduce_segments<F>(id, xs.data(), G2, V, M, ss.data(), tt.data());
   const uint32_t nn = msmk::subset_n1(lgP, fan);  // 1
-  std::vector<uint32_t> sub((size_t)G * K * nn * 4 * FW);
-  for (uint32_t id = 0; id < G * K * nn; ++id) msmk::subset_first<F>(id, ss.data(), tt.data(), G, lgP, fan, sub.data());
-  // host fold (same as prover.hip msm_fold)
+  std::vector<uint32_t> sub((size_t)G2 * K * nn * 4 * FW);
+  for (uint32_t id = 0; id < G2 * K * nn; ++id) msmk::subset_first<F>(id, ss.data(), tt.data(), G2, lgP, fan, sub.data());
+  // host fold (same as device_pipeline.hip msm_fold)
   auto ld = [&](uint32_t w) {
     const uint32_t* p = sub.data() + (size_t)w * 4 * FW;
     if constexpr (FW == 8)
@@ -87,11 +105,16 @@ static host::Jac<HF> run(std::vector<uint32_t>& pts, std::vector<uint32_t>& sc, 
       return host::jac_from_xyzz(f2(p), f2(p + 16), f2(p + 32), f2(p + 48));
     }
   };
-  auto group = [&](uint32_t g) {
-    host::Jac<HF> a = lgP > 0 ? ld(g * K + lgP - 1) : host::Jac<HF>::inf();
-    for (int b = (int)lgP - 2; b >= 0; --b) a = host::jac_add(host::jac_dbl(a), ld(g * K + b));
+  auto subgroup = [&](uint32_t s) {
+    host::Jac<HF> a = lgP > 0 ? ld(s * K + lgP - 1) : host::Jac<HF>::inf();
+    for (int b = (int)lgP - 2; b >= 0; --b) a = host::jac_add(host::jac_dbl(a), ld(s * K + b));
     for (int i = 0; i < prm.lg_m(); ++i) a = host::jac_dbl(a);
-    return host::jac_add(a, ld(g * K + lgP));
+    return host::jac_add(a, ld(s * K + lgP));
+  };
+  auto group = [&](uint32_t g) {
+    host::Jac<HF> a = subgroup(2 * g);
+    for (int i = 0; i < prm.lgV(); ++i) a = host::jac_dbl(a);
+    return host::jac_add(a, subgroup(2 * g + 1));
   };
   host::Jac<HF> r = group(G - 1);
   for (int g = (int)G - 2; g >= 0; --g) {

@@ -31,7 +31,7 @@ def kind(name, grid, wg):
             return "k_accumulate B2"
         return "k_accumulate (grid %d)" % (grid // wg)
     for k in ("k_ntt<0", "k_ntt<1", "k_ntt<2", "k_build_abc", "k_join_abc", "k_hs_scatter1", "k_witness_unpack",
-              "k_merge_final", "k_reduce_segments", "k_subset"):
+              "k_merge_final", "k_rowcol", "k_reduce_segments", "k_subset"):
         if k in name.replace(" ", ""):
             return k
     return None

@@ -30,7 +30,7 @@ def klass(name):
         return "NTT"
     if re.search(r"k_(build_abc|join_abc)", n):
         return "QAP (buildABC, joinABC)"
-    if re.search(r"k_(merge|reduce_segments|subset)", n):
+    if re.search(r"k_(merge|rowcol|reduce_segments|subset)", n):
         return "MSM finish (merges, reduction, subset sums)"
     if re.search(r"k_(hs_|scan_|tlen|lvl|digits|plan)", n):
         return "MSM plans (bucket sort, tasks)"

@@ -32,12 +32,19 @@ Jac<F> msm_fold(const uint32_t* win, const MsmParams& p) {
     return host::jac_from_xyzz(f_from_dev<F>(q), f_from_dev<F>(q + FW), f_from_dev<F>(q + 2 * FW),
                                f_from_dev<F>(q + 3 * FW));
   };
+  // sub-group s (K points): sum_p T_p + M sum_b 2^b Q_b; group g: its column sums' sub-group plus V times
+  // its row sums'
   const int K = p.K(), lgP = p.lgP();
-  auto group = [&](int g) {
-    Jac<F> acc = lgP > 0 ? load((size_t)g * K + lgP - 1) : Jac<F>::inf();
-    for (int b = lgP - 2; b >= 0; --b) acc = host::jac_add(host::jac_dbl(acc), load((size_t)g * K + b));
+  auto sub = [&](int s) {
+    Jac<F> acc = lgP > 0 ? load((size_t)s * K + lgP - 1) : Jac<F>::inf();
+    for (int b = lgP - 2; b >= 0; --b) acc = host::jac_add(host::jac_dbl(acc), load((size_t)s * K + b));
     for (int i = 0; i < p.lg_m(); ++i) acc = host::jac_dbl(acc);
-    return host::jac_add(acc, load((size_t)g * K + lgP));
+    return host::jac_add(acc, load((size_t)s * K + lgP));
+  };
+  auto group = [&](int g) {
+    Jac<F> acc = sub(2 * g);
+    for (int i = 0; i < p.lgV(); ++i) acc = host::jac_dbl(acc);
+    return host::jac_add(acc, sub(2 * g + 1));
   };
   Jac<F> r = group(p.groups - 1);
   for (int g = p.groups - 2; g >= 0; --g) {
@@ -162,7 +169,7 @@ MsmParams make_params(size_t n, int c, int depth, int scalar_bits) {
 
 void apply_task_options(MsmParams& p, int task, const MsmOptions& o) {
   p.S = task > 0 ? task : 48;
-  if (o.seg > 0 && o.seg <= (1 << (p.c - 1))) p.M = o.seg;
+  if (o.seg > 0 && o.seg <= p.V()) p.M = o.seg;
 }
 
 // MSM parameters for a prover: window bits automatic (ZKP_MSM w= / h= override); table depth = W

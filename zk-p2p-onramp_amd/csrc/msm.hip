@@ -148,6 +148,16 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(MergeWaves<
   msmk::merge_final<F>(blockIdx.x * TPB + threadIdx.x, part0, part1, off, nb, S2, levels, buckets);
 }
 template <class F>
+__global__ __launch_bounds__(TPB) void k_rowcol_chain(const uint32_t* __restrict__ buckets, const msmk::RowCol rc,
+                                                      uint32_t* __restrict__ part, uint32_t* __restrict__ sums) {
+  msmk::rowcol_chain<F>(blockIdx.x * TPB + threadIdx.x, buckets, rc, part, sums);
+}
+template <class F>
+__global__ __launch_bounds__(TPB) void k_rowcol_tree(const uint32_t* __restrict__ part, const msmk::RowCol rc,
+                                                     uint32_t* __restrict__ sums) {
+  msmk::rowcol_tree<F>(blockIdx.x * TPB + threadIdx.x, part, rc, sums);
+}
+template <class F>
 __global__ __launch_bounds__(TPB) void k_reduce_segments(const uint32_t* __restrict__ buckets, uint32_t G,
                                                          uint32_t half, uint32_t M, uint32_t* __restrict__ s_out,
                                                          uint32_t* __restrict__ t_out) {
@@ -174,8 +184,8 @@ __global__ __launch_bounds__(msmk::TREE_TPB) void k_subset_tree_next(
   __shared__ uint32_t lds[msmk::XyzzLimbs<F>::N * (msmk::TREE_TPB / 2)];
   msmk::subset_tree_next<F>(in, n_in, n_out, blockIdx.y, blockIdx.x, lds, out);
 }
-// largest first-level tree grid (workgroups): larger subset sums (the proof's H MSM: 18 sums of 2^16
-// values) start with a full-lane fan-in chain level (profiles/subset_tree_r02.txt)
+// largest first-level tree grid (workgroups): larger subset sums (segments of one or two points:
+// ZKP_MSM seg=) start with a full-lane fan-in chain level (profiles/subset_tree_r02.txt)
 constexpr size_t TREE_FIRST_MAX = 512;
 
 // count (or, with rank != nullptr, claim a slot for) one entry in LDS counter h[b]; lanes of a
@@ -214,13 +224,17 @@ void run_accumulate(const MsmPlan& plan, const MsmBases& bases, uint32_t* part_a
   HIPX(hipGetLastError());
 }
 
+// the first level's geometry for the engine's kernels
+inline msmk::RowCol rowcol_for(const MsmParams& p) {
+  return msmk::rowcol_make((uint32_t)p.groups, (uint32_t)p.U(), (uint32_t)p.V(), msmk::ROWCOL_CHAIN, msmk::ROWCOL_SPAN);
+}
+
 template <class F>
-void run_finish(const MsmPlan& plan, uint32_t* part_a, uint32_t* part_b, uint32_t* buckets, uint32_t* seg_s,
-                uint32_t* seg_t, uint32_t* const sub[2], uint32_t* d_out, hipStream_t st) {
+void run_finish(const MsmPlan& plan, uint32_t* part_a, uint32_t* part_b, uint32_t* buckets, uint32_t* rc_part,
+                uint32_t* rc_sums, uint32_t* seg_s, uint32_t* seg_t, uint32_t* const sub[2], uint32_t* d_out,
+                hipStream_t st) {
   const MsmParams& prm = plan.params();
   const uint32_t nb = (uint32_t)prm.buckets();
-  const uint32_t half = (uint32_t)prm.half();
-  const uint32_t G = (uint32_t)prm.groups;
   const size_t xyzz_bytes = 16 * (size_t)FWords<F>::W;
   size_t bound = plan.max_tasks_now();
   for (int lv = 0; lv < plan.merge_levels() && plan.entries() > 0; ++lv) {
@@ -232,10 +246,18 @@ void run_finish(const MsmPlan& plan, uint32_t* part_a, uint32_t* part_b, uint32_
   }
   hipLaunchKernelGGL(k_merge_final<F>, dim3(grid_for(nb)), dim3(TPB), 0, st, part_a, part_b, plan.task_off(), nb,
                      (uint32_t)prm.S2, plan.merge_levels(), buckets);
-  // bucket reduction: segments, then the K = lgP + 1 subset sums per group by L-ary tree
+  // bucket reduction, first level: every group's row and column sums (chains, then a shuffle tree)
+  const msmk::RowCol rc = rowcol_for(prm);
+  hipLaunchKernelGGL(k_rowcol_chain<F>, dim3(grid_for((size_t)rc.row_parts() + rc.col_parts())), dim3(TPB), 0, st,
+                     buckets, rc, rc_part, rc_sums);
+  hipLaunchKernelGGL(k_rowcol_tree<F>, dim3(grid_for((size_t)rc.row_lanes() + rc.col_lanes())), dim3(TPB), 0, st,
+                     rc_part, rc, rc_sums);
+  // second level, over the G = 2 * groups sub-groups of V points: segments, then the K = lgP + 1 subset
+  // sums per sub-group
+  const uint32_t G = (uint32_t)prm.subgroups(), V = (uint32_t)prm.V();
   const uint32_t M = (uint32_t)prm.M, lgP = (uint32_t)prm.lgP(), K = (uint32_t)prm.K();
-  hipLaunchKernelGGL(k_reduce_segments<F>, dim3(grid_for((size_t)G * (half / M))), dim3(TPB), 0, st, buckets, G, half,
-                     M, seg_s, seg_t);
+  hipLaunchKernelGGL(k_reduce_segments<F>, dim3(grid_for((size_t)G * (V / M))), dim3(TPB), 0, st, rc_sums, G, V, M,
+                     seg_s, seg_t);
   // workgroup LDS trees: 2 * TREE_TPB values per workgroup and launch level
   int cur = 0;
   constexpr uint32_t CH = 2 * msmk::TREE_TPB;
@@ -243,8 +265,8 @@ void run_finish(const MsmPlan& plan, uint32_t* part_a, uint32_t* part_b, uint32_
   if ((size_t)G * K * n <= TREE_FIRST_MAX) {  // about one round of workgroups: the tree from the inputs
     hipLaunchKernelGGL(k_subset_tree_first<F>, dim3(n, G * K), dim3(msmk::TREE_TPB), 0, st, seg_s, seg_t, lgP, n,
                        sub[0]);
-  } else {  // many inputs (the H MSM: K x 2^16): a full-lane fan-in chain level first (short: the
-            // trees above it take the rest), then trees
+  } else {  // many inputs: a full-lane fan-in chain level first (short: the trees above it take the
+            // rest), then trees
     const uint32_t cf = msmk::TREE_CHAIN_FAN;
     n = (((1u << lgP) + 2 * cf - 1) / (2 * cf));
     hipLaunchKernelGGL(k_subset_first<F>, dim3(grid_for((size_t)G * K * n)), dim3(TPB), 0, st, seg_s, seg_t, G, lgP,
@@ -657,19 +679,20 @@ void MsmPlan::build_shared(MsmPlan* const plans[PlanMembership::NPLAN], const ui
 MsmEngine::MsmEngine(Curve curve, const MsmParams& prm, size_t max_n, hipStream_t stream)
     : curve_(curve), prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream) {
   fwords_ = curve_fwords(curve);
-  const size_t half = prm_.half();
   nbuckets_ = prm_.buckets();
   max_tasks_ = (max_n_ * prm_.windows + prm_.S - 1) / prm_.S + nbuckets_;
   const size_t xyzz_words = 4 * (size_t)fwords_;
   part_a_ = DevBuf<>(max_tasks_ * xyzz_words);
   part_b_ = DevBuf<>(max_tasks_ * xyzz_words);
   buckets_ = DevBuf<>(nbuckets_ * xyzz_words);
-  const size_t nseg = (size_t)prm_.groups * (half / prm_.M);
+  const msmk::RowCol rc = rowcol_for(prm_);
+  rc_part_ = DevBuf<>(((size_t)rc.row_parts() + rc.col_parts()) * xyzz_words);
+  rc_ = DevBuf<>((size_t)prm_.subgroups() * prm_.V() * xyzz_words);
+  const size_t P = (size_t)prm_.V() / prm_.M, nseg = (size_t)prm_.subgroups() * P;
   seg_s_ = DevBuf<>(nseg * xyzz_words);
   seg_t_ = DevBuf<>(nseg * xyzz_words);
-  const size_t n1 = (size_t)prm_.groups * prm_.K() *
-                    std::max(((half / prm_.M) + 2 * msmk::TREE_CHAIN_FAN - 1) / (2 * msmk::TREE_CHAIN_FAN),
-                             ((half / prm_.M) + 2 * msmk::TREE_TPB - 1) / (2 * msmk::TREE_TPB));
+  const size_t n1 = prm_.out_points() * std::max((P + 2 * msmk::TREE_CHAIN_FAN - 1) / (2 * msmk::TREE_CHAIN_FAN),
+                                                 (P + 2 * msmk::TREE_TPB - 1) / (2 * msmk::TREE_TPB));
   for (int i = 0; i < 2; ++i) sub_[i] = DevBuf<>(n1 * xyzz_words);
   for (auto& e : ev_) e[0] = Event(true), e[1] = Event(true);
   h_counts_ = PinnedBuf<uint32_t>(2 * MAX_PENDING);
@@ -719,9 +742,9 @@ void MsmEngine::finish(const MsmPlan& plan, uint32_t* d_out, hipStream_t st) {
   if (!st) st = stream_;
   uint32_t* const sub[2] = {sub_[0], sub_[1]};
   if (curve_ == Curve::G1)
-    run_finish<Fq>(plan, part_a_, part_b_, buckets_, seg_s_, seg_t_, sub, d_out, st);
+    run_finish<Fq>(plan, part_a_, part_b_, buckets_, rc_part_, rc_, seg_s_, seg_t_, sub, d_out, st);
   else
-    run_finish<Fq2>(plan, part_a_, part_b_, buckets_, seg_s_, seg_t_, sub, d_out, st);
+    run_finish<Fq2>(plan, part_a_, part_b_, buckets_, rc_part_, rc_, seg_s_, seg_t_, sub, d_out, st);
 }
 
 void MsmEngine::run(const MsmPlan& plan, const MsmBases& bases, uint32_t* d_out) {

@@ -31,11 +31,14 @@
 //     5. merge  : buckets with more than 2*S2 task partials are folded by segmented
 //                 merge levels that skip the light buckets; one thread per bucket
 //                 sums what is left.
-//     6. reduce : per group, sum_k (k+1) B_k = sum_p T_p + M sum_b 2^b Q_b from
-//                 segment running sums (S_p, T_p over M buckets) and bit-subset
-//                 sums Q_b = sum_{p: bit b} S_p, all plain L-ary tree sums.
-//     7. out    : G x K points (XYZZ, device layout); the host applies the 2^b, M
-//                 and group (2^(c T g)) weights by Horner (msm_fold).
+//     6. reduce : per group, with the 2^(c-1) buckets as U rows of V = 2^ceil((c-1)/2) (k = u V + v),
+//                 sum_k (k+1) B_k = V sum_u u rho_u + sum_v (v+1) kappa_v  from the row sums rho_u and
+//                 the column sums kappa_v: two additions per bucket (a chain per thread, then a
+//                 shuffle tree per wave).  The two weighted sums over <= V points each (sub-groups
+//                 2g: rho_1.., 2g+1: kappa) are sum_p T_p + M sum_b 2^b Q_b from segment running
+//                 sums (S_p, T_p over M points) and bit-subset sums Q_b = sum_{p: bit b} S_p.
+//     7. out    : 2G x K points (XYZZ, device layout); the host applies the 2^b, M, V and group
+//                 (2^(c T g)) weights by Horner (msm_fold).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -56,7 +59,7 @@ struct MsmParams {
   int groups = 1;    // G = ceil(W / T) bucket groups
   int S = 32;        // max entries per accumulate task
   int S2 = 4;        // fan-in of a heavy-bucket merge level (short chains: latency-bound)
-  int M = 4;         // buckets per reduction segment (running sums)
+  int M = 4;         // row / column sums per reduction segment (running sums)
   // bits the windows cover: 255 = any scalar below r plus the signed-digit carry.  A caller whose
   // scalars are all below 2^b passes b + 1 and gets ceil((b + 1) / c) windows: no digits, buckets or
   // reductions for the windows above (zkey_verify.hip: 128-bit coefficients, 129)
@@ -80,15 +83,22 @@ struct MsmParams {
     p.windows = (scalar_bits + p.c - 1) / p.c;
     p.depth = depth_override > 0 ? (depth_override < p.windows ? depth_override : p.windows) : p.windows;
     p.groups = (p.windows + p.depth - 1) / p.depth;
-    if (p.M > (1 << (p.c - 1))) p.M = 1 << (p.c - 1);
+    if (p.M > p.V()) p.M = p.V();
     return p;
   }
-  // reduction output: per group, lgP subset sums Q_b and sum_p T_p (P = 2^(c-1) / M segments)
-  int lg_m() const { int l = 0; while ((1 << l) < M) ++l; return l; }
-  int lgP() const { return c - 1 - lg_m(); }
-  int K() const { return lgP() + 1; }
   size_t half() const { return size_t(1) << (c - 1); }
   size_t buckets() const { return (size_t)groups * half(); }
+  // a group's buckets as U rows of V: bucket k = u V + v, V = 2^ceil((c-1)/2) >= U
+  int lgV() const { return c / 2; }
+  int V() const { return 1 << lgV(); }
+  int U() const { return 1 << (c - 1 - lgV()); }
+  // every group reduces to two sub-groups of V points (its row sums, then its column sums), each of
+  // which leaves lgP subset sums Q_b and sum_p T_p (P = V / M segments): K points
+  int subgroups() const { return 2 * groups; }
+  int lg_m() const { int l = 0; while ((1 << l) < M) ++l; return l; }
+  int lgP() const { return lgV() - lg_m(); }
+  int K() const { return lgP() + 1; }
+  size_t out_points() const { return (size_t)subgroups() * K(); }
 };
 
 // Window bits for a DENSE plan (hand-written bucket sort) near c.  The top window of a 254-bit
@@ -281,7 +291,7 @@ class MsmEngine {
 
   // sum_i s_i * P_i for the plan's scalars over the bases (bases.n() == plan.n(),
   // same c and depth).  Waits for plan.ready() on the engine's stream, enqueues
-  // everything there; the G group sums (XYZZ, device layout, window_words() words)
+  // everything there; the 2G x K sub-group sums (XYZZ, device layout, window_words() words)
   // land in d_out (device).  Nothing is synchronised.
   void run(const MsmPlan& plan, const MsmBases& bases, uint32_t* d_out);
   // the same in two phases: accumulate() on the engine's stream (bucket-task partial sums),
@@ -291,7 +301,7 @@ class MsmEngine {
   void accumulate(const MsmPlan& plan, const MsmBases& bases);
   void finish(const MsmPlan& plan, uint32_t* d_out, hipStream_t st = nullptr);
   size_t window_words() const { return window_words_for(curve_, prm_); }
-  static size_t window_words_for(Curve c, const MsmParams& p) { return (size_t)p.groups * p.K() * 4 * curve_fwords(c); }
+  static size_t window_words_for(Curve c, const MsmParams& p) { return p.out_points() * 4 * curve_fwords(c); }
 
   // Kernel instrumentation (HIP events on this engine's stream).  When enabled,
   // every run() brackets the bucket-accumulate kernel with events; collect()
@@ -322,6 +332,7 @@ class MsmEngine {
   size_t nbuckets_ = 0, max_tasks_ = 0;
   int fwords_;
   DevBuf<> part_a_, part_b_, buckets_;
+  DevBuf<> rc_part_, rc_;  // row / column chain partials; the 2G sub-groups of V row and column sums
   DevBuf<> seg_s_, seg_t_, sub_[2];
   static constexpr int MAX_PENDING = 16;
   bool instrument_ = false;

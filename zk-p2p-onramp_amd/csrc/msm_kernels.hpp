@@ -213,11 +213,82 @@ ZDEV void merge_final(uint32_t b, const uint32_t* __restrict__ part0, const uint
   store_xyzz(buckets, b, acc);
 }
 
-// ---- bucket reduction:  sum_k (k+1) B_k over the 2^(c-1) buckets of a group, as
-//   sum_p T_p + M * sum_b 2^b Q_b   with  S_p = sum_j B_(pM+j),  T_p = sum_j (j+1) B_(pM+j)
-//   (segments of M buckets) and Q_b = sum of S_p over the p with bit b set.
+// ---- bucket reduction, first level:  sum_k (k+1) B_k over the H = 2^(c-1) buckets of a group, taken
+// as U rows of V (k = u V + v), is
+//   V * sum_u u rho_u + sum_v (v+1) kappa_v   with  rho_u = sum_v B_(uV+v),  kappa_v = sum_u B_(uV+v):
+// every bucket enters one row sum and one column sum, two additions per bucket.  A thread sums a
+// chain of Lr consecutive buckets of a row or Lc buckets V apart of a column; a wave then sums up to
+// ROWCOL_SPAN such partials by shuffles (rowcol_tree).  What is left per group are two weighted sums
+// of the shape above over V points each (the sub-groups 2g: X_j = rho_(j+1), padded with infinity,
+// and 2g+1: X_v = kappa_v), which the second level below reduces.
+constexpr uint32_t ROWCOL_CHAIN = 8;   // chain length of a first-level partial
+constexpr uint32_t ROWCOL_SPAN = 128;  // partials one wave of rowcol_tree sums: two per lane
+struct RowCol {
+  uint32_t G, U, V;  // groups; rows and columns of a group's buckets
+  uint32_t Lr, Lc;   // buckets per row / column partial
+  ZDEV uint32_t nr() const { return V / Lr; }  // partials per row (a power of two)
+  ZDEV uint32_t nc() const { return U / Lc; }  // partials per column
+  ZDEV uint32_t row_parts() const { return G * U * nr(); }
+  ZDEV uint32_t col_parts() const { return G * V * nc(); }
+  // rowcol_tree: a lane takes two partials (one when a sum has a single partial); the columns'
+  // lanes start at a wave boundary
+  ZDEV uint32_t row_lanes() const { return (row_parts() / (nr() >= 2 ? 2u : 1u) + 63u) & ~63u; }
+  ZDEV uint32_t col_lanes() const { return col_parts() / (nc() >= 2 ? 2u : 1u); }
+};
+// chains of L buckets, longer where a row or column would leave more than `span` partials
+ZDEV RowCol rowcol_make(uint32_t G, uint32_t U, uint32_t V, uint32_t L, uint32_t span) {
+  RowCol rc;
+  rc.G = G, rc.U = U, rc.V = V;
+  rc.Lr = umin(V, L > V / span ? L : V / span);
+  rc.Lc = umin(U, L > U / span ? L : U / span);
+  return rc;
+}
+constexpr uint32_t ROWCOL_NONE = 0xffffffffu;
+// where sum `seg` (rows g * U + u first, then columns G * U + g * V + v) goes among the 2G sub-groups
+// of V points; row 0 has weight 0 and no place
+ZDEV uint32_t rowcol_slot(uint32_t seg, const RowCol& rc) {
+  if (seg < rc.G * rc.U) {
+    const uint32_t g = seg / rc.U, u = seg - g * rc.U;
+    return u == 0 ? ROWCOL_NONE : 2 * g * rc.V + u - 1;
+  }
+  const uint32_t s = seg - rc.G * rc.U, g = s / rc.V, v = s - g * rc.V;
+  return (2 * g + 1) * rc.V + v;
+}
+
+// partial `id`: rows first (partial q of row u of group g at (g U + u) nr + q: Lr consecutive
+// buckets), then columns (partial q of column v at row_parts + (g V + v) nc + q; neighbouring threads
+// take neighbouring columns).  The threads of row 0 write the infinity padding of their group's row
+// sub-group (slots U-1 .. V-1 of `sums`) instead.
+template <class FS>
+ZDEV void rowcol_chain(uint32_t id, const uint32_t* __restrict__ buckets, const RowCol rc,
+                       uint32_t* __restrict__ part, uint32_t* __restrict__ sums) {
+  using F = typename MergeField<FS>::type;
+  const uint32_t nr = rc.nr(), nc = rc.nc(), rp = rc.row_parts();
+  if (id < rp) {
+    const uint32_t row = id / nr, q = id - row * nr, g = row / rc.U, u = row - g * rc.U;
+    if (u == 0) {
+      for (uint32_t j = rc.U - 1 + q; j < rc.V; j += nr) store_xyzz(sums, (size_t)2 * g * rc.V + j, xyzz_inf<F>());
+      return;
+    }
+    const size_t b0 = (size_t)id * rc.Lr;
+    Xyzz<F> acc = load_xyzz<F>(buckets, b0);
+    for (uint32_t i = 1; i < rc.Lr; ++i) xyzz_add(acc, load_xyzz<F>(buckets, b0 + i));
+    store_xyzz(part, id, acc);
+  } else if (id - rp < rc.col_parts()) {
+    const uint32_t k = id - rp, t = k / rc.V, v = k - t * rc.V, g = t / nc, q = t - g * nc;
+    const size_t b0 = ((size_t)g * rc.U + (size_t)q * rc.Lc) * rc.V + v;
+    Xyzz<F> acc = load_xyzz<F>(buckets, b0);
+    for (uint32_t i = 1; i < rc.Lc; ++i) xyzz_add(acc, load_xyzz<F>(buckets, b0 + (size_t)i * rc.V));
+    store_xyzz(part, (size_t)rp + ((size_t)g * rc.V + v) * nc + q, acc);
+  }
+}
+
+// ---- second level:  sum_k (k+1) X_k over the V points of a sub-group, as
+//   sum_p T_p + M * sum_b 2^b Q_b   with  S_p = sum_j X_(pM+j),  T_p = sum_j (j+1) X_(pM+j)
+//   (segments of M points) and Q_b = sum of S_p over the p with bit b set.
 // Every piece is a plain sum (no doublings inside the tree), so the latency is a few
 // short add chains instead of one long running sum; the host applies the 2^b / M weights.
+// (`buckets`, G and half below: the sub-groups' points, their number and V.)
 
 // segment p of group g (one thread): S_p, T_p by running sums over M buckets
 template <class FS>
@@ -370,6 +441,47 @@ __device__ __forceinline__ void subset_tree_next(const uint32_t* __restrict__ in
   }
   v = wg_tree_sum(v, lds);
   if (threadIdx.x == 0) store_xyzz(out, (size_t)seg * n_out + chunk, v);
+}
+
+// ---- row and column sums from their partials, by shuffles: lane t takes two neighbouring partials of
+// one sum (rows first; the columns' lanes start at row_lanes()), the n / 2 <= 64 lanes of a sum
+// add up by a butterfly, and its first lane stores the sum at its rowcol_slot.  No LDS and no idle
+// waves: a wave finishes 128 / n sums with log2(n) additions.
+template <class C>
+__device__ __forceinline__ Fe<C> shfl_xor_f(const Fe<C>& x, int m) {
+  Fe<C> r;
+#pragma unroll
+  for (int l = 0; l < NL; ++l) r.v[l] = (uint32_t)__shfl_xor((int)x.v[l], m);
+  return r;
+}
+template <class C>
+__device__ __forceinline__ Fq2T<C> shfl_xor_f(const Fq2T<C>& x, int m) {
+  return Fq2T<C>{shfl_xor_f(x.c0, m), shfl_xor_f(x.c1, m)};
+}
+template <class F>
+__device__ __forceinline__ void rowcol_tree(uint32_t t, const uint32_t* __restrict__ part, const RowCol rc,
+                                            uint32_t* __restrict__ sums) {
+  const uint32_t rl = rc.row_lanes();
+  const bool col = t >= rl;  // the same for a whole wave
+  const uint32_t n = col ? rc.nc() : rc.nr(), e = n >= 2 ? 2u : 1u;
+  const uint32_t i = (col ? t - rl : t) * e;  // the lane's first partial among the rows' or the columns'
+  const uint32_t slot = i < (col ? rc.col_parts() : rc.row_parts()) ? rowcol_slot(i / n + (col ? rc.G * rc.U : 0u), rc)
+                                                                   : ROWCOL_NONE;
+  Xyzz<F> v = xyzz_inf<F>();
+  if (slot != ROWCOL_NONE) {
+    const size_t p = (size_t)(col ? rc.row_parts() : 0u) + i;
+    v = load_xyzz<F>(part, p);
+    if (e == 2) xyzz_add(v, load_xyzz<F>(part, p + 1));
+  }
+  for (uint32_t m = 1; m < n / e; m <<= 1) {
+    Xyzz<F> q;
+    q.x = shfl_xor_f(v.x, (int)m);
+    q.y = shfl_xor_f(v.y, (int)m);
+    q.zz = shfl_xor_f(v.zz, (int)m);
+    q.zzz = shfl_xor_f(v.zzz, (int)m);
+    xyzz_add(v, q);
+  }
+  if (slot != ROWCOL_NONE && i % n == 0) store_xyzz(sums, slot, v);
 }
 
 }  // namespace msmk
