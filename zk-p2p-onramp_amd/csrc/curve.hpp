@@ -13,7 +13,17 @@
 #pragma once
 #include "field.hpp"
 
+// Event hook of the three additions: names the exceptional branch taken (DBL: equal operands, doubling;
+// CANCEL: opposite operands, infinity; ACC_INF / Q_INF: an operand at infinity).  Empty unless the
+// including file defined it first (tools/hosttest/msm_emu.cpp counts the events per pipeline stage), so
+// device code does not see it.
+#ifndef ZKP_XYZZ_EVENT
+#define ZKP_XYZZ_EVENT(kind)
+#endif
+
 namespace zkp {
+
+enum XyzzEvent { XYZZ_EV_DBL = 0, XYZZ_EV_CANCEL = 1, XYZZ_EV_ACC_INF = 2, XYZZ_EV_Q_INF = 3, XYZZ_EV_KINDS = 4 };
 
 template <class F>
 struct Aff {
@@ -171,10 +181,14 @@ ZDEV void xyzz_add_aff(Xyzz<F>& acc, const Aff<F>& q, bool neg = false) {
   // the exceptional cases (a base at infinity, an empty accumulator, P = +-Q below) are screened
   // by their low limb first: the exact tests run only where it allows them, never on the common path
   if (lo_zero(q.x) && lo_zero(q.y)) {
-    if (aff_is_inf(q)) return;
+    if (aff_is_inf(q)) {
+      ZKP_XYZZ_EVENT(XYZZ_EV_Q_INF);
+      return;
+    }
   }
   if (lo_zero(acc.zz)) {
     if (xyzz_is_inf(acc)) {
+      ZKP_XYZZ_EVENT(XYZZ_EV_ACC_INF);
       acc.x = q.x;
       acc.y = neg ? sub(f_zero<F>(), q.y) : q.y;
       acc.zz = f_one<F>();
@@ -192,10 +206,12 @@ ZDEV void xyzz_add_aff(Xyzz<F>& acc, const Aff<F>& q, bool neg = false) {
   if (maybe_zero(PP)) {
     if (is_zero(PP)) {
       if (is_zero(RR)) {
+        ZKP_XYZZ_EVENT(XYZZ_EV_DBL);
         Aff<F> qs = q;
         if (neg) qs.y = sub(f_zero<F>(), q.y);
         acc = xyzz_dbl_aff(qs);
       } else {
+        ZKP_XYZZ_EVENT(XYZZ_EV_CANCEL);
         acc = xyzz_inf<F>();
       }
       return;
@@ -218,7 +234,7 @@ ZDEV void xyzz_add_aff(Xyzz<F>& acc, const Aff<F>& q, bool neg = false) {
 template <class F>
 ZDEV Xyzz<F> xyzz_from_aff_pair(const Aff<F>& p, bool np, const Aff<F>& q, bool nq) {
   Xyzz<F> acc = xyzz_inf<F>();
-  if (aff_is_inf(p) || aff_is_inf(q)) {
+  if (aff_is_inf(p) || aff_is_inf(q)) {  // the events: those of the two mixed additions
     xyzz_add_aff(acc, p, np);
     xyzz_add_aff(acc, q, nq);
     return acc;
@@ -230,7 +246,11 @@ ZDEV Xyzz<F> xyzz_from_aff_pair(const Aff<F>& p, bool np, const Aff<F>& q, bool 
   F PP = acc_sqr(P);
   F RR = acc_sqr(R);
   if (is_zero(PP)) {
-    if (is_zero(RR)) return xyzz_dbl_aff(Aff<F>{p.x, py});
+    if (is_zero(RR)) {
+      ZKP_XYZZ_EVENT(XYZZ_EV_DBL);
+      return xyzz_dbl_aff(Aff<F>{p.x, py});
+    }
+    ZKP_XYZZ_EVENT(XYZZ_EV_CANCEL);
     return acc;  // p == -q
   }
   F PPP = mul(P, PP);
@@ -245,8 +265,12 @@ ZDEV Xyzz<F> xyzz_from_aff_pair(const Aff<F>& p, bool np, const Aff<F>& q, bool 
 // acc += q (both XYZZ) — add-2008-s, with the same lazy subtractions as xyzz_add_aff
 template <class F>
 ZDEV void xyzz_add(Xyzz<F>& acc, const Xyzz<F>& q) {
-  if (xyzz_is_inf(q)) return;
+  if (xyzz_is_inf(q)) {
+    ZKP_XYZZ_EVENT(XYZZ_EV_Q_INF);
+    return;
+  }
   if (xyzz_is_inf(acc)) {
+    ZKP_XYZZ_EVENT(XYZZ_EV_ACC_INF);
     acc = q;
     return;
   }
@@ -258,10 +282,13 @@ ZDEV void xyzz_add(Xyzz<F>& acc, const Xyzz<F>& q) {
   F PP, RR;
   acc_sqr_2(P, R, PP, RR);
   if (is_zero(PP)) {
-    if (is_zero(RR))
+    if (is_zero(RR)) {
+      ZKP_XYZZ_EVENT(XYZZ_EV_DBL);
       acc = xyzz_dbl(acc);
-    else
+    } else {
+      ZKP_XYZZ_EVENT(XYZZ_EV_CANCEL);
       acc = xyzz_inf<F>();
+    }
     return;
   }
   F PPP, Q;

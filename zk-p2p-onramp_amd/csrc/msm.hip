@@ -184,9 +184,6 @@ __global__ __launch_bounds__(msmk::TREE_TPB) void k_subset_tree_next(
   __shared__ uint32_t lds[msmk::XyzzLimbs<F>::N * (msmk::TREE_TPB / 2)];
   msmk::subset_tree_next<F>(in, n_in, n_out, blockIdx.y, blockIdx.x, lds, out);
 }
-// largest first-level tree grid (workgroups): larger subset sums (segments of one or two points:
-// ZKP_MSM seg=) start with a full-lane fan-in chain level (profiles/subset_tree_r02.txt)
-constexpr size_t TREE_FIRST_MAX = 512;
 
 // count (or, with rank != nullptr, claim a slot for) one entry in LDS counter h[b]; lanes of a
 // wave that all hit the same counter (the skewed buckets of 0/1 witness values) use one atomic
@@ -262,7 +259,7 @@ void run_finish(const MsmPlan& plan, uint32_t* part_a, uint32_t* part_b, uint32_
   int cur = 0;
   constexpr uint32_t CH = 2 * msmk::TREE_TPB;
   uint32_t n = ((1u << lgP) + CH - 1) / CH;
-  if ((size_t)G * K * n <= TREE_FIRST_MAX) {  // about one round of workgroups: the tree from the inputs
+  if ((size_t)G * K * n <= msmk::TREE_FIRST_MAX) {  // about one round of workgroups: the tree from the inputs
     hipLaunchKernelGGL(k_subset_tree_first<F>, dim3(n, G * K), dim3(msmk::TREE_TPB), 0, st, seg_s, seg_t, lgP, n,
                        sub[0]);
   } else {  // many inputs: a full-lane fan-in chain level first (short: the trees above it take the

@@ -3,6 +3,12 @@
 #pragma once
 #include "curve.hpp"
 
+// Names the running sum the next addition of reduce_segments belongs to (its two sums alternate inside
+// one loop), for a replay that counts curve.hpp's ZKP_XYZZ_EVENT per stage; empty otherwise.
+#ifndef ZKP_MSM_STAGE
+#define ZKP_MSM_STAGE(tag)
+#endif
+
 namespace zkp {
 namespace msmk {
 
@@ -300,7 +306,9 @@ ZDEV void reduce_segments(uint32_t id, const uint32_t* __restrict__ buckets, uin
   const uint32_t g = id / P, p = id - g * P;
   Xyzz<F> R = xyzz_inf<F>(), T = xyzz_inf<F>();
   for (int j = (int)M - 1; j >= 0; --j) {
+    ZKP_MSM_STAGE(REDUCE_R);
     xyzz_add(R, load_xyzz<F>(buckets, (size_t)g * half + (size_t)p * M + (uint32_t)j));
+    ZKP_MSM_STAGE(REDUCE_T);
     xyzz_add(T, R);
   }
   store_xyzz(s_out, id, R);
@@ -345,6 +353,9 @@ ZDEV void subset_first(uint32_t id, const uint32_t* __restrict__ s_in, const uin
 // sequential full addition costs ~5 us on a lightly loaded SIMD).
 constexpr int TREE_TPB = 256;
 constexpr uint32_t TREE_CHAIN_FAN = 4;  // fan-in of the chain level below the trees (large subset sums)
+// largest first-level tree grid (workgroups): larger subset sums (segments of one or two points:
+// ZKP_MSM seg=) start with a full-lane fan-in chain level (profiles/subset_tree_r02.txt)
+constexpr size_t TREE_FIRST_MAX = 512;
 template <class F>
 struct XyzzLimbs;  // 32-bit words of one XYZZ point in the 9-limb compute form
 template <>
