@@ -133,6 +133,26 @@ zkp_status zkp_blake2b512(const uint8_t* data, size_t len, uint8_t* out64);
 zkp_status zkp_zkey_new(int device, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len,
                         uint8_t** out, size_t* out_len);
 
+/* Setup acceleration: `snarkjs powersoftau prepare phase2 <pot_beacon.ptau> <pot_final.ptau>` (reference
+ * circuit/scripts/generate_keys_phase1.sh:20; the step circuit/scripts/generate_keys_phase2_groth16.sh:7
+ * asks about) on `device`: the Lagrange sections 12-15 that zkp_zkey_new reads.  For every level
+ * p = 0..power the first 2^p points of sections 2, 3, 4, 5 go through a group inverse FFT
+ * (zkp_group_ifft); level p lands at point offset 2^p - 1 of lTauG1 (12), lTauG2 (13), lAlphaTauG1 (14),
+ * lBetaTauG1 (15).  The input needs sections 1-7 of a bn128 ptau (v1) with the sizes its power gives;
+ * every point of sections 2-5 must have canonical coordinates and be on its curve or all-zero, else
+ * ZKP_ERR_FORMAT "ptau: section <id> point <i> is not on the curve" (the smallest such i; no subgroup
+ * check: that is `powersoftau verify`).  The output holds sections 1-7 copied byte for byte in that
+ * order, then 12, 13, 14, 15; sections 12-15 of the input are ignored and rebuilt, any other section id
+ * is not copied.  A power whose working set does not fit in free HBM is ZKP_ERR_OUT_OF_MEMORY before
+ * any launch.  Layout restated (oracle/binfile.py write_ptau), parity unpinned.
+ * *out: the prepared ptau (zkp_buffer_free). */
+zkp_status zkp_ptau_prepare_phase2(int device, const uint8_t* ptau, size_t len, uint8_t** out, size_t* out_len);
+/* ms of the last zkp_ptau_prepare_phase2 on this thread: [0] total, [1] parse + point check, [2] upload
+ * (host wall), [3] G1 iFFT (all levels, three vectors), [4] G2 iFFT, [5] affine conversion (the levels
+ * above one workgroup; the small levels convert inside their one launch, counted in [3] / [4]),
+ * [6] download (host wall; overlaps the next level), [7] kernel launches.  n = capacity of ms. */
+zkp_status zkp_ptau_prepare_timings(double* ms, int n);
+
 /* Setup acceleration: `snarkjs zkey verify`, the gate of every phase-2 ceremony (reference
  * circuit/scripts/generate_keys_phase2_groth16.sh:26, circuit/server-scripts/
  * generate_keys_phase2_groth16.sh:56, generate_chunked_keys_phase2_groth16.sh:68,
@@ -285,6 +305,11 @@ zkp_status zkp_msm(int device, int g2, const uint8_t* points, const uint8_t* sca
  * zkp_rlc_g1: sum_i coeff(first_index + i) * a_i and the same over b_i (G1, zkey layout) under one
  * MSM plan, after zkp_points_check of both (a bad point is a ZKP_ERR_INVALID_ARG). */
 zkp_status zkp_rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_index, size_t n, uint8_t* out);
+/* The kernel of zkp_ptau_prepare_phase2 on one vector: out_c = n^-1 sum_j w^(-c j) P_j for the
+ * n = 2^log_n points (zkey layout; g2: 128 bytes each; log_n <= 28) at `points`, w = Fr.w[log_n], natural
+ * order in and out; out: n points.  For P_j = tau^j G this is L_c(tau) G.  Every exceptional addition
+ * (infinity, equal and opposite operands) is computed, not assumed away. */
+zkp_status zkp_group_ifft(int device, int g2, const uint8_t* points, int log_n, uint8_t* out);
 zkp_status zkp_points_check(int device, int g2, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad);
 zkp_status zkp_rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* points_a,
                       const uint8_t* points_b, size_t n, uint8_t* out_a64, int* inf_a, uint8_t* out_b64, int* inf_b);

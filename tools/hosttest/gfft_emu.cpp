@@ -1,0 +1,115 @@
+// CPU replay of the group inverse FFT (gfft_kernels.hpp per-thread bodies, the launches of
+// ptau_prepare.hip in the device's stage order) for checking it without a GPU.
+// usage: gfft_emu <g1|g2> <file of 2^log_n zkey-layout points> <log_n> [--events] [--window 1|2]
+//   -> one line per output point, natural order: the affine coordinates (decimal) or `inf`
+//   --events: after them a `geometry` line and one `event <stage> <dbl> <cancel> <acc_inf> <q_inf>` line
+//     per stage: how often the additions of that stage took an exceptional branch (curve.hpp
+//     ZKP_XYZZ_EVENT), the additions inside the scalar multiplications included
+//   --window W: the scalar multiplications' window bits (gfft::scale; default 2, as the device)
+// A level of at most Geom::TILE points is one workgroup: load, every stage on the tile, finish.  A larger
+// one runs the first Geom::LG stages tile by tile, the remaining stages over the whole vector, one
+// launch each, then the finish launch.
+#include <array>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+static std::vector<std::string> g_stage_names;
+static std::vector<std::array<unsigned long long, 4>> g_events;
+static int g_stage = 0;
+static void set_stage(const std::string& name) {
+  for (size_t i = 0; i < g_stage_names.size(); ++i)
+    if (g_stage_names[i] == name) {
+      g_stage = (int)i;
+      return;
+    }
+  g_stage_names.push_back(name);
+  g_events.push_back({0, 0, 0, 0});
+  g_stage = (int)g_stage_names.size() - 1;
+}
+static inline void emu_event(int kind) { ++g_events[g_stage][kind]; }
+#define ZKP_XYZZ_EVENT(kind) ::emu_event((int)(kind))
+#include "../../zk-p2p-onramp_amd/csrc/gfft_kernels.hpp"
+#include "../../zk-p2p-onramp_amd/csrc/host_ec.hpp"
+using namespace zkp;
+
+template <class F, int WB>
+static std::vector<uint32_t> run(const std::vector<uint32_t>& in, int p) {
+  using G = gfft::Geom<F>;
+  constexpr int W = G::W;
+  const size_t n = (size_t)1 << p;
+  std::vector<uint32_t> tw((size_t)gfft::TW_ENTRIES * 8), out(n * 2 * W), work(n * 4 * W);
+  set_stage("table");
+  gfft::fill_table(tw.data());
+  const int l = p < G::LG ? p : G::LG;
+  const size_t cnt = (size_t)1 << l;
+  std::vector<uint32_t> lds(G::LDS_WORDS);
+  for (size_t tile = 0; tile < n / cnt; ++tile) {
+    set_stage("load");
+    for (size_t q = 0; q < cnt; ++q) store_xyzz(lds.data(), q, gfft::load_point<F>(in.data(), gfft::brev(tile * cnt + q, p)));
+    for (int s = 0; s < l; ++s) {
+      set_stage("stage." + std::to_string(s));
+      for (size_t i = 0; i < cnt / 2; ++i) gfft::stage<F, WB>(lds.data(), tw.data(), p, s, i);
+    }
+    for (size_t q = 0; q < cnt; ++q) store_xyzz(work.data(), tile * cnt + q, load_xyzz<F>(lds.data(), q));
+  }
+  for (int s = l; s < p; ++s) {
+    set_stage("stage." + std::to_string(s));
+    for (size_t i = 0; i < n / 2; ++i) gfft::stage<F, WB>(work.data(), tw.data(), p, s, i);
+  }
+  set_stage("finish");
+  for (size_t i = 0; i < n; ++i) gfft::finish<F>(load_xyzz<F>(work.data(), i), tw.data(), out.data(), i);
+  return out;
+}
+
+static std::string dec(const uint32_t* w) {  // a zkey-layout coordinate (Montgomery 2^256) in decimal
+  host::U256 v;
+  std::memcpy(v.w, w, 32);
+  return host::u256_to_dec(host::Fq::raw(v).to_std());
+}
+
+int main(int argc, char** argv) {
+  std::vector<const char*> pos;
+  bool events = false;
+  int window = 2;
+  for (int i = 1; i < argc; ++i) {
+    if (!strcmp(argv[i], "--events")) events = true;
+    else if (!strcmp(argv[i], "--window") && i + 1 < argc) window = atoi(argv[++i]);
+    else pos.push_back(argv[i]);
+  }
+  if (pos.size() != 3 || (window != 1 && window != 2)) {
+    fprintf(stderr, "usage: gfft_emu <g1|g2> <file> <log_n> [--events] [--window 1|2]\n");
+    return 2;
+  }
+  const bool g2 = std::string(pos[0]) == "g2";
+  const int p = atoi(pos[2]);
+  if (p < 0 || p > 20) return 2;
+  const size_t n = (size_t)1 << p, pw = g2 ? 32 : 16;
+  std::vector<uint32_t> in(n * pw);
+  FILE* f = fopen(pos[1], "rb");
+  if (!f || fread(in.data(), 4, in.size(), f) != in.size()) return 1;
+  fclose(f);
+  const std::vector<uint32_t> out = g2 ? (window == 2 ? run<Fq2, 2>(in, p) : run<Fq2, 1>(in, p))
+                                       : (window == 2 ? run<Fq, 2>(in, p) : run<Fq, 1>(in, p));
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t* q = out.data() + i * pw;
+    bool inf = true;
+    for (size_t j = 0; j < pw; ++j) inf &= q[j] == 0;
+    if (inf) {
+      printf("inf\n");
+      continue;
+    }
+    for (size_t c = 0; c < pw / 8; ++c) printf("%s%s", c ? " " : "", dec(q + c * 8).c_str());
+    printf("\n");
+  }
+  if (events) {
+    printf("geometry tile=%d local_stages=%d global_stages=%d\n", g2 ? gfft::Geom<Fq2>::TILE : gfft::Geom<Fq>::TILE,
+           p < (g2 ? gfft::Geom<Fq2>::LG : gfft::Geom<Fq>::LG) ? p : (g2 ? gfft::Geom<Fq2>::LG : gfft::Geom<Fq>::LG),
+           p < (g2 ? gfft::Geom<Fq2>::LG : gfft::Geom<Fq>::LG) ? 0 : p - (g2 ? gfft::Geom<Fq2>::LG : gfft::Geom<Fq>::LG));
+    for (size_t i = 0; i < g_stage_names.size(); ++i)
+      printf("event %s %llu %llu %llu %llu\n", g_stage_names[i].c_str(), g_events[i][0], g_events[i][1], g_events[i][2],
+             g_events[i][3]);
+  }
+  return 0;
+}

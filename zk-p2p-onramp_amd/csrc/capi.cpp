@@ -394,6 +394,26 @@ zkp_status zkp_zkey_verify_timings(double* ms, int n) {
   return ZKP_OK;
 }
 
+zkp_status zkp_ptau_prepare_phase2(int device, const uint8_t* ptau, size_t len, uint8_t** out, size_t* out_len) {
+  if (!ptau || !out || !out_len) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] { buf = zkp::ptau_prepare_phase2(device, ptau, len); });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_ptau_prepare_timings(double* ms, int n) {
+  if (!ms || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const zkp::PrepareTimings t = zkp::ptau_prepare_timings();
+  const double v[8] = {t.total_ms, t.parse_check_ms, t.upload_ms, t.g1_ms, t.g2_ms, t.affine_ms, t.download_ms, t.launches};
+  for (int i = 0; i < n && i < 8; ++i) ms[i] = v[i];
+  return ZKP_OK;
+}
+
+zkp_status zkp_group_ifft(int device, int g2, const uint8_t* points, int log_n, uint8_t* out) {
+  if (!points || !out) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::group_ifft(device, g2 != 0, points, log_n, out); });
+}
+
 zkp_status zkp_rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_index, size_t n, uint8_t* out) {
   if (!seed32 || (n && !out)) return fail(ZKP_ERR_INVALID_ARG, "null argument");
   return guard([&] { zkp::rlc_coeffs(device, seed32, first_index, n, out); });

@@ -155,6 +155,24 @@ std::vector<uint8_t> zkey_apply_delta(int device, const uint8_t* zkey, size_t le
 // `snarkjs zkey new`: the phase-2 starting key (gamma = delta = 1) of a circom .r1cs from a
 // prepared .ptau (sections 12-15), the point sections built on `device` (zkey_new.hip)
 std::vector<uint8_t> zkey_new(int device, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* ptau, size_t ptau_len);
+// `snarkjs powersoftau prepare phase2`: the ptau with its Lagrange sections 12-15, every level a group
+// inverse FFT on `device` (ptau_prepare.hip)
+std::vector<uint8_t> ptau_prepare_phase2(int device, const uint8_t* ptau, size_t len);
+// ms of the last ptau_prepare_phase2 on this thread
+struct PrepareTimings {
+  double total_ms = 0;        // host wall of the whole call
+  double parse_check_ms = 0;  // parsing and assembling the copied sections (host) + the point check (device)
+  double upload_ms = 0;       // host wall of the section uploads
+  double g1_ms = 0;           // G1 iFFT, all levels, three vectors (device); the small levels' launch whole
+  double g2_ms = 0;           // G2 iFFT
+  double affine_ms = 0;       // the affine launches of the levels above one workgroup, G1 and G2
+  double download_ms = 0;     // host wall of the downloads (they overlap the next level's computation)
+  double launches = 0;        // kernel launches of the transforms
+};
+PrepareTimings ptau_prepare_timings();
+// out_c = n^-1 sum_j w^(-c j) P_j over n = 2^log_n zkey-layout points (w = Fr.w[log_n]), natural order
+// in and out, through the kernels of ptau_prepare_phase2
+void group_ifft(int device, bool g2, const uint8_t* points, int log_n, uint8_t* out);
 
 // kernel-level helpers (C-ABI zkp_msm_g1/g2, zkp_ntt_fr)
 // c / depth: window bits and base-table depth (0 = automatic, as the prover)

@@ -229,6 +229,13 @@ void points_check(int device, bool g2, const uint8_t* points, size_t n, uint64_t
   *n_bad = h[0], *first_bad = h[1];
 }
 
+void points_bad_reset(unsigned long long* bad, hipStream_t st) { reset_bad(bad, 1, st); }
+
+void points_check_resident(bool g2, const uint32_t* d_points, size_t n, uint64_t base, unsigned long long* bad,
+                           hipStream_t st) {
+  launch_check(g2, d_points, n, base, curve_b(g2), bad, st);
+}
+
 RlcResult rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* a, const uint8_t* b,
                  size_t n) {
   const auto t_begin = std::chrono::steady_clock::now();

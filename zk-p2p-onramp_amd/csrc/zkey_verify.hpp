@@ -10,6 +10,8 @@
 // uniform 128-bit values: a section that is not the initial one times delta_init / delta passes with
 // probability <= 2^-128, and the MSM runs ceil(129 / c) windows instead of ceil(255 / c).
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -56,6 +58,11 @@ void rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_index, size_t 
 // zkey-layout points (G1 64 bytes, G2 128): *n_bad of them are not canonical (a coordinate >= p) or
 // neither all-zero nor on the curve; *first_bad: the smallest such index (RLC_NO_BAD if none)
 void points_check(int device, bool g2, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad);
+// the same check of n points already in HBM (as uploaded, zkey layout), queued on st: bad[0] += the bad
+// points, bad[1] = min(bad[1], base + i) over them (two device words; points_bad_reset sets 0 and ~0)
+void points_bad_reset(unsigned long long* bad, hipStream_t st);
+void points_check_resident(bool g2, const uint32_t* d_points, size_t n, uint64_t base, unsigned long long* bad,
+                           hipStream_t st);
 RlcResult rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* a, const uint8_t* b, size_t n);
 
 // timings of one zkey_verify_frominit (ms)

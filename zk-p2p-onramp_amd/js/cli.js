@@ -14,16 +14,19 @@
  *   node cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]
  * and the gate of the ceremony (reference circuit/scripts/generate_keys_phase2_groth16.sh:26):
  *   node cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>
+ * and the last step of phase 1 (reference circuit/scripts/generate_keys_phase1.sh:20), whose output `zkey new` reads:
+ *   node cli.js powersoftau prepare phase2 <pot_beacon.ptau> <pot_final.ptau> [-v]
  */
 const fs = require('fs');
-const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, release } = require('./groth16');
+const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, release } = require('./groth16');
 
 const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n' +
               '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
               '       cli.js groth16 setup|zkey new <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>\n' +
               '       cli.js zkey contribute <in.zkey> <out.zkey> -e=<entropy> [-n=name]\n' +
               '       cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]\n' +
-              '       cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n';
+              '       cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n' +
+              '       cli.js powersoftau prepare phase2 <in.ptau> <out.ptau> [-v]\n';
 
 async function main(argv) {
   if (argv.length === 5 && argv[0] === 'zkey' && argv[1] === 'export' && argv[2] === 'soliditycalldata') {
@@ -38,6 +41,10 @@ async function main(argv) {
     return 0;
   }
   const named = argv.filter((a) => !/^(-n|--name)=/.test(a) && a !== '-v' && a !== '--verbose');
+  if (named.length === 5 && argv[0] === 'powersoftau' && argv[1] === 'prepare' && argv[2] === 'phase2') {
+    await preparePhase2(named[3], named[4]);
+    return 0;
+  }
   if (named.length === 5 && argv[0] === 'zkey' && argv[1] === 'verify') {
     // snarkjs' log lines (recalled from snarkjs 0.4.22, unpinned): "[INFO]  snarkJS: ZKey Ok!" and exit 0,
     // else the reason and "[ERROR] snarkJS: Invalid zkey" and exit 1

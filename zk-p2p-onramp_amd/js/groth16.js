@@ -181,6 +181,20 @@ async function newZKey(r1csName, ptauName, zkeyName, logger, device) {
 }
 
 /*
+ * snarkjs' `powersOfTau.preparePhase2(oldPtauFilename, newPTauFilename, logger)` (the `powersoftau prepare
+ * phase2` step, reference circuit/scripts/generate_keys_phase1.sh:20): the Lagrange sections 12-15 that
+ * `zkey new` reads, every level a group inverse FFT on the GPU.  The input is a path or a {type:"mem"}
+ * descriptor; with an output name the file is written there, and its bytes are returned either way.
+ */
+async function preparePhase2(oldPtauName, newPtauName, logger, device) {
+  const out = addon.ptauPreparePhase2(readInput(oldPtauName), device || 0);
+  if (typeof newPtauName === 'string') fs.writeFileSync(newPtauName, out);
+  else if (newPtauName && typeof newPtauName === 'object' && newPtauName.type === 'mem') newPtauName.data = out;
+  if (logger && logger.info) logger.info(`powersoftau prepare phase2: ${out.length} bytes`);
+  return out;
+}
+
+/*
  * snarkjs' `zKey.beacon(zkeyNameOld, zkeyNameNew, name, beaconHashStr, numIterationsExp, logger)`
  * (reference dizkus-scripts/3_gen_chunk_zkey.sh:36): delta -> k delta, L/H -> k^-1 on the GPU, with
  * k and the contribution record (section 10: proof of knowledge, transcript, beacon parameters,
@@ -259,6 +273,8 @@ module.exports = {
   groth16: { prove, proveBatch },
   proveBatch,
   zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit },
+  powersOfTau: { preparePhase2 },
+  preparePhase2,
   verifyFromR1cs,
   verifyFromInit,
   newZKey,

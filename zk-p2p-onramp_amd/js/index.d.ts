@@ -37,6 +37,14 @@ export declare const zKey: {
   /** the same against the initial key `zkey new` wrote */
   verifyFromInit(initName: Input, zkeyName: Input, logger?: VerifyLogger, device?: number): Promise<boolean>;
 };
+export declare const powersOfTau: {
+  /** `snarkjs powersoftau prepare phase2` on the GPU: the ptau with its Lagrange sections 12-15 (what
+   *  `zkey new` reads); writes newPtauName when given, returns the file's bytes */
+  preparePhase2(oldPtauName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array }, logger?: Logger,
+                device?: number): Promise<Buffer>;
+};
+export declare function preparePhase2(oldPtauName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array },
+                                      logger?: Logger, device?: number): Promise<Buffer>;
 export interface VerifyLogger extends Logger { error?(msg: string): void }
 export declare function verifyFromR1cs(r1csName: Input, ptauName: Input, zkeyName: Input, logger?: VerifyLogger,
                                        device?: number): Promise<boolean>;

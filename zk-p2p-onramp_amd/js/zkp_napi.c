@@ -10,6 +10,7 @@
  *                                                    every proof attempted, per-proof errors)
  *   freeProver(handle)
  *   zkeyNew(r1csBuffer, ptauBuffer, device?)     -> Buffer (`snarkjs zkey new`, synchronous)
+ *   ptauPreparePhase2(ptauBuffer, device?)       -> Buffer (`snarkjs powersoftau prepare phase2`, synchronous)
  *   zkeyBeacon(zkeyBuffer, beaconBuffer, numIterationsExp, device?, name?) -> Buffer (`zkey beacon`)
  *   zkeyContribute(zkeyBuffer, entropy, name?, device?) -> Buffer (`zkey contribute`)
  *   zkeyVerify(initBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify` against the initial key)
@@ -106,6 +107,39 @@ static napi_value js_zkey_new(napi_env env, napi_callback_info info) {
   uint8_t* out = NULL;
   size_t out_len = 0;
   zkp_status st = zkp_zkey_new(device, (const uint8_t*)r1cs, r1cs_len, (const uint8_t*)ptau, ptau_len, &out, &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  napi_value buf;
+  void* dst = NULL;
+  napi_status ns = napi_create_buffer(env, out_len, &dst, &buf);
+  if (ns == napi_ok) memcpy(dst, out, out_len);
+  zkp_buffer_free(out);
+  if (ns != napi_ok) {
+    napi_throw_error(env, NULL, "N-API call failed: napi_create_buffer");
+    return NULL;
+  }
+  return buf;
+}
+
+/* ptauPreparePhase2(ptauBuffer, device?) -> Buffer: `snarkjs powersoftau prepare phase2`
+ * (zkp_ptau_prepare_phase2), synchronous -- a setup step */
+static napi_value js_ptau_prepare_phase2(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &b0);
+  if (!b0) {
+    napi_throw_type_error(env, NULL, "ptauPreparePhase2(ptauBuffer, device?)");
+    return NULL;
+  }
+  int device = 0;
+  if (argc > 1) napi_get_value_int32(env, argv[1], &device);
+  void* ptau;
+  size_t ptau_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &ptau, &ptau_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  zkp_status st = zkp_ptau_prepare_phase2(device, (const uint8_t*)ptau, ptau_len, &out, &out_len);
   if (st != ZKP_OK) return throw_status(env, st);
   napi_value buf;
   void* dst = NULL;
@@ -640,6 +674,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"proveBatch", NULL, js_prove_batch, NULL, NULL, NULL, napi_default, NULL},
       {"freeProver", NULL, js_free, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyNew", NULL, js_zkey_new, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauPreparePhase2", NULL, js_ptau_prepare_phase2, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyBeacon", NULL, js_zkey_beacon, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyContribute", NULL, js_zkey_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerify", NULL, js_zkey_verify, NULL, NULL, NULL, napi_default, NULL},

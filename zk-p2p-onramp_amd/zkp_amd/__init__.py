@@ -125,6 +125,11 @@ def load_library(path: str = LIB_PATH):
                                              ctypes.POINTER(sz)]
         lib.zkp_zkey_contribute.argtypes = [ctypes.c_int, u8p, sz, u8p, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
         lib.zkp_zkey_new.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+        lib.zkp_ptau_prepare_phase2.argtypes = [ctypes.c_int, u8p, sz, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+        lib.zkp_ptau_prepare_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+        lib.zkp_group_ifft.argtypes = [ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int, u8p]
+        for name in ("zkp_ptau_prepare_phase2", "zkp_ptau_prepare_timings", "zkp_group_ifft"):
+            getattr(lib, name).restype = ctypes.c_int
         lib.zkp_beacon_secret.argtypes = [u8p, sz, ctypes.c_uint32, u8p]
         lib.zkp_zkey_beacon.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, ctypes.c_uint32, ctypes.POINTER(u8p),
                                         ctypes.POINTER(sz)]
@@ -639,6 +644,42 @@ def zkey_new(r1cs: bytes, ptau: bytes, device: int = 0) -> bytes:
         return _copy_out(out, n.value)
     finally:
         lib.zkp_buffer_free(out)
+
+
+def ptau_prepare_phase2(ptau: bytes, device: int = 0) -> bytes:
+    """`snarkjs powersoftau prepare phase2 <in.ptau> <out.ptau>` (zkp_ptau_prepare_phase2): the ptau with
+    its Lagrange sections 12-15, which zkey_new reads; every level is a group inverse FFT on the GPU.
+    Sections 1-7 are copied, 12-15 of the input ignored and rebuilt, other ids dropped."""
+    lib = load_library()
+    pp, plen, pk = _in(ptau)
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_ptau_prepare_phase2(device, pp, plen, ctypes.byref(out), ctypes.byref(n)))
+    try:
+        return _copy_out(out, n.value)
+    finally:
+        lib.zkp_buffer_free(out)
+
+
+def ptau_prepare_timings() -> dict:
+    """ms of the calling thread's last ptau_prepare_phase2 (zkp_ptau_prepare_timings)."""
+    out = (ctypes.c_double * 8)()
+    _check(load_library().zkp_ptau_prepare_timings(out, 8))
+    keys = ["total", "parse_point_check", "upload", "g1_ifft", "g2_ifft", "affine", "download", "launches"]
+    return dict(zip(keys, list(out)))
+
+
+def group_ifft(points: bytes, log_n: int, g2: bool = False, device: int = 0) -> bytes:
+    """Kernel-level (zkp_group_ifft): out_c = n^-1 sum_j w^(-c j) P_j over the n = 2^log_n zkey-layout
+    points (w = Fr.w[log_n]), natural order in and out."""
+    pb = 128 if g2 else 64
+    if log_n < 0 or len(points) != pb << log_n:
+        raise ValueError("group_ifft: points must hold 2^log_n points of %d bytes" % pb)
+    pp, pk = _buf(points)
+    out = (ctypes.c_uint8 * len(points))()
+    _check(load_library().zkp_group_ifft(device, 1 if g2 else 0, pp, log_n,
+                                         ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8))))
+    return bytes(out)
 
 
 def _seed(seed):
