@@ -141,7 +141,7 @@ zkp_status zkp_zkey_new(int device, const uint8_t* r1cs, size_t r1cs_len, const 
  * lBetaTauG1 (15).  The input needs sections 1-7 of a bn128 ptau (v1) with the sizes its power gives;
  * every point of sections 2-5 must have canonical coordinates and be on its curve or all-zero, else
  * ZKP_ERR_FORMAT "ptau: section <id> point <i> is not on the curve" (the smallest such i; no subgroup
- * check: that is `powersoftau verify`).  The output holds sections 1-7 copied byte for byte in that
+ * check: that is zkp_ptau_verify_sections).  The output holds sections 1-7 copied byte for byte in that
  * order, then 12, 13, 14, 15; sections 12-15 of the input are ignored and rebuilt, any other section id
  * is not copied.  A power whose working set does not fit in free HBM is ZKP_ERR_OUT_OF_MEMORY before
  * any launch.  Layout restated (oracle/binfile.py write_ptau), parity unpinned.
@@ -152,6 +152,57 @@ zkp_status zkp_ptau_prepare_phase2(int device, const uint8_t* ptau, size_t len, 
  * above one workgroup; the small levels convert inside their one launch, counted in [3] / [4]),
  * [6] download (host wall; overlaps the next level), [7] kernel launches.  n = capacity of ms. */
 zkp_status zkp_ptau_prepare_timings(double* ms, int n);
+
+/* Setup acceleration: the point sections of `snarkjs powersoftau verify <ptau>` (reference
+ * circuit/scripts/generate_keys_phase1.sh:16; commented out as too slow in generate_keys_phase2_groth16.sh:3
+ * and generate_keys_phase2_plonk.sh:3) on `device`, of sections 2-6 and, if present, 12-15 (the project's
+ * layout: 2^(power+1) - 1 points each, oracle/binfile.py write_ptau); section 7 is not read beyond its
+ * presence.  In order, the first failing check gives the message:
+ *  1. every point has canonical coordinates and is all-zero or on its curve ("section <id> point <i> is
+ *     not on the curve": the smallest i of the smallest id); every G2 point (sections 3, 6, 13) is
+ *     all-zero or in the subgroup of order r ("section <id> point <i> is not in the subgroup");
+ *  2. tauG1[0], tauG2[0] are the generators ("First element of tau*G1 section must be the generator",
+ *     "... tau*G2 ..."); tauG1[1], tauG2[1], alphaTauG1[0], betaTauG1[0], betaG2 are not infinity;
+ *  3. powers: random linear combinations of adjacent points and one pairing check per section
+ *     ("tauG1 section. Powers do not match", tauG2, alphaTauG1, betaTauG1; "betaG2 does not match
+ *     betaTauG1");
+ *  4. every Lagrange section against its tau section ("Lagrange section <id> does not match section
+ *     <id'> at level <p>": the smallest failing level).
+ * Status and verdict as zkp_zkey_verify: the status reports only a malformed file (bad magic or version,
+ * n8 != 32, power outside 1..28, ceremonyPower < power, a section 2-7 missing or not the size its power
+ * gives, sections 12-15 present in part or of another size: ZKP_ERR_FORMAT naming the section; another
+ * prime: ZKP_ERR_CURVE), a working set beyond free HBM (ZKP_ERR_OUT_OF_MEMORY before any launch) or a
+ * device error; a file that fails a check is ZKP_OK with *valid = 0.  seed32 and ZKP_VERIFY_CHUNK as
+ * zkp_zkey_verify (PRODUCTION PASSES NULL).  Lagrange sections are checked up to power 27. */
+zkp_status zkp_ptau_verify_sections(int device, const uint8_t* ptau, size_t len, const uint8_t* seed32 /* NULL: OS CSPRNG */,
+                                    int* valid, char* msg, size_t msg_cap);
+/* `snarkjs powersoftau verify <ptau>` whole: the contribution chain of section 7 on the host, then the above.
+ * Section 7 is a u32 count and that many records: tauG1, tauG2, alphaG1, betaG1, betaG2 (LEM points); the
+ * public key's nine points (tau, alpha, beta: g1_s, g1_sx each, then the three g2_spx); partialHash (216
+ * bytes, a Blake2b-512 state in progress: h[8], t, f, the 128-byte buffer, its fill, u64 LE each);
+ * nextChallenge (64); type (u32: 0 contribute, 1 beacon); a u32 parameter length and the parameters as in
+ * section 10 of a zkey.  Layout and hashes restated from snarkjs 0.4.22, parity unpinned; the model that
+ * fixes them is tests/helpers/ptau_model.py.  A record cut short, a length that runs past the section's
+ * end, a coordinate >= p, a malformed partialHash, a beacon without parameters or with numIterationsExp
+ * > 63 are ZKP_ERR_FORMAT naming section 7.  Verdicts, in this order: no contribution ("This file has no
+ * contribution! It cannot be used in production"); the last contribution against the one before it
+ * (a beacon's key re-drawn: "BEACON key (tauG1_s) is not generated correctly" ...; "INVALID key (tau)" /
+ * (alpha) / (beta); "INVALID tau*G1. contribution", tau*G2, alpha*G1, beta*G1, beta*G2); its five points
+ * against the sections ("Second element of tau*G1 section does not match the one in the contribution
+ * section" ...); the sections (above); if power = ceremonyPower, Blake2b(responseHash || sections 2-6
+ * uncompressed) against the last nextChallenge ("Hash of the values does not match the next challenge of
+ * the last contributor in the contributions section"); the earlier contributions, last but one first.
+ * The first contribution is checked against the first challenge: a Blake2b over 384 * 2^ceremonyPower
+ * bytes (about 100 GB at 28), hashed on a host thread beside the device work. */
+zkp_status zkp_ptau_verify(int device, const uint8_t* ptau, size_t len, const uint8_t* seed32 /* NULL: OS CSPRNG (production) */,
+                           int* valid, char* msg, size_t msg_cap);
+/* ms of the last zkp_ptau_verify / zkp_ptau_verify_sections on this thread: [0] total, [1] parse (host), [2] uploads (host
+ * wall; they overlap the checks), [3] point check, [4] G2 subgroup check, [5] coefficients, [6] Lagrange
+ * scalars (NTT + fold), [7] base conversion + plans, [8] accumulate + finish of the pair sums, [9] of the
+ * Lagrange side (129-bit), [10] of the tau side (255-bit), [11] host folds, [12] host pairings,
+ * [13] chunks; zkp_ptau_verify only (host): [14] the contributions' checks, [15] the first challenge hash
+ * (its own thread), [16] the next-challenge hash.  n = capacity of ms. */
+zkp_status zkp_ptau_verify_timings(double* ms, int n);
 
 /* Setup acceleration: `snarkjs zkey verify`, the gate of every phase-2 ceremony (reference
  * circuit/scripts/generate_keys_phase2_groth16.sh:26, circuit/server-scripts/
@@ -313,6 +364,15 @@ zkp_status zkp_group_ifft(int device, int g2, const uint8_t* points, int log_n, 
 zkp_status zkp_points_check(int device, int g2, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad);
 zkp_status zkp_rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* points_a,
                       const uint8_t* points_b, size_t n, uint8_t* out_a64, int* inf_a, uint8_t* out_b64, int* inf_b);
+/* The device parts of zkp_ptau_verify_sections, each on its own.
+ * zkp_g2_subgroup_check: *n_bad = the G2 points (zkey layout, on the curve) that are neither all-zero nor
+ * of order r; *first_bad = the smallest such index (UINT64_MAX if none).
+ * zkp_rlc_pairs: A = sum_{i<n-1} r_i P_i and B = sum_{i<n-1} r_i P_(i+1) under one MSM plan, r_i =
+ * coefficient first_index + i of zkp_rlc_coeffs; out_a / out_b: 64 bytes (g2: 128), affine standard-form
+ * LE; n <= 1 gives two infinities; a point off its curve is a ZKP_ERR_INVALID_ARG. */
+zkp_status zkp_g2_subgroup_check(int device, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad);
+zkp_status zkp_rlc_pairs(int device, int g2, const uint8_t* seed32, uint64_t first_index, const uint8_t* points, size_t n,
+                         uint8_t* out_a, int* inf_a, uint8_t* out_b, int* inf_b);
 /* In-place Fr transforms on n = 2^k standard-form LE elements, natural order:
  * mode 0: forward (A_j = sum a_i w^ij), 1: inverse, 2: coset-extend (snarkjs
  * ifft -> batchApplyKey(1, Fr.w[k+1]) -> fft). */

@@ -25,6 +25,7 @@
 #include "host_pairing.hpp"
 #include "mpc.hpp"
 #include "prover.hpp"
+#include "ptau_verify.hpp"
 #include "zkey_io.hpp"
 #include "zkey_verify.hpp"
 
@@ -437,6 +438,61 @@ zkp_status zkp_rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, c
                               (r.first_bad_a != zkp::RLC_NO_BAD ? " of set a" : " of set b") + " is not on the curve");
     *inf_a = zkp::jac_to_bytes_g1(r.sum_a, out_a64) ? 0 : 1;
     *inf_b = zkp::jac_to_bytes_g1(r.sum_b, out_b64) ? 0 : 1;
+  });
+}
+
+zkp_status zkp_ptau_verify_sections(int device, const uint8_t* ptau, size_t len, const uint8_t* seed32, int* valid, char* msg,
+                                    size_t msg_cap) {
+  if (!ptau || !len || !valid) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  *valid = 0;
+  put_msg("", msg, msg_cap);
+  return guard([&] {
+    std::string m;
+    *valid = zkp::ptau_verify_sections(device, ptau, len, seed32, m) ? 1 : 0;
+    put_msg(m, msg, msg_cap);
+  });
+}
+
+zkp_status zkp_ptau_verify(int device, const uint8_t* ptau, size_t len, const uint8_t* seed32, int* valid, char* msg,
+                           size_t msg_cap) {
+  if (!ptau || !len || !valid) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  *valid = 0;
+  put_msg("", msg, msg_cap);
+  return guard([&] {
+    std::string m;
+    *valid = zkp::ptau_verify(device, ptau, len, seed32, m) ? 1 : 0;
+    put_msg(m, msg, msg_cap);
+  });
+}
+
+zkp_status zkp_ptau_verify_timings(double* ms, int n) {
+  if (!ms || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const zkp::PtauVerifyTimings t = zkp::ptau_verify_timings();
+  const double v[17] = {t.total_ms,   t.parse_ms,        t.upload_ms,          t.check_ms,          t.subgroup_ms,
+                        t.coeffs_ms,  t.ntt_ms,          t.plan_ms,            t.acc_pairs_ms,      t.acc_lag_ms,
+                        t.acc_tau_ms, t.fold_ms,         t.pairing_ms,         (double)t.chunks,    t.contributions_ms,
+                        t.first_challenge_ms, t.next_challenge_ms};
+  for (int i = 0; i < n && i < 17; ++i) ms[i] = v[i];
+  return ZKP_OK;
+}
+
+zkp_status zkp_g2_subgroup_check(int device, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad) {
+  if ((n && !points) || !n_bad || !first_bad) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::g2_subgroup_check(device, points, n, n_bad, first_bad); });
+}
+
+zkp_status zkp_rlc_pairs(int device, int g2, const uint8_t* seed32, uint64_t first_index, const uint8_t* points, size_t n,
+                         uint8_t* out_a, int* inf_a, uint8_t* out_b, int* inf_b) {
+  if (!seed32 || (n && !points) || !out_a || !inf_a || !out_b || !inf_b) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] {
+    const zkp::PairSums r = zkp::rlc_pairs(device, g2 != 0, seed32, first_index, points, n);
+    if (g2) {
+      *inf_a = zkp::jac_to_bytes_g2(r.a2, out_a) ? 0 : 1;
+      *inf_b = zkp::jac_to_bytes_g2(r.b2, out_b) ? 0 : 1;
+    } else {
+      *inf_a = zkp::jac_to_bytes_g1(r.a1, out_a) ? 0 : 1;
+      *inf_b = zkp::jac_to_bytes_g1(r.b1, out_b) ? 0 : 1;
+    }
   });
 }
 

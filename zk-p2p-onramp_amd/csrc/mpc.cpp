@@ -10,6 +10,7 @@
 #include "beacon.hpp"
 #include "host_pairing.hpp"
 #include "prover.hpp"
+#include "ptau_verify.hpp"
 #include "zkey_verify.hpp"
 
 namespace zkp {
@@ -612,8 +613,6 @@ void binfile_replace_section(std::vector<uint8_t>& file, uint32_t id, const std:
 }
 
 // ---------------------------------------------------------------- zkey verify
-namespace {
-
 // e(g1a, g2b) == e(g1b, g2a); false if any point is the point at infinity
 bool same_ratio(const Affine<HFq>& g1a, const Affine<HFq>& g1b, const Affine<HFq2>& g2a, const Affine<HFq2>& g2b) {
   if (g1a.inf || g1b.inf || g2a.inf || g2b.inf) return false;
@@ -621,12 +620,6 @@ bool same_ratio(const Affine<HFq>& g1a, const Affine<HFq>& g1b, const Affine<HFq
   const Affine<HFq2> qs[2] = {g2b, g2a};
   return host::fq12_is_one(host::final_exponentiation(host::miller_loop_multi(ps, qs, 2)));
 }
-template <class F>
-bool same_point(const Affine<F>& a, const Affine<F>& b) {
-  return a.inf == b.inf && (a.inf || (a.x == b.x && a.y == b.y));
-}
-bool g2_valid(const Affine<HFq2>& p) { return host::g2_on_curve(p) && host::g2_in_subgroup(p); }
-
 Affine<HFq2> g2_generator() {  // Verifier.sol:33-36
   auto fq = [](const char* dec) {
     U256 v{{0, 0, 0, 0}};
@@ -646,6 +639,14 @@ Affine<HFq2> g2_generator() {  // Verifier.sol:33-36
                            fq("4082367875863433681332203403145435568316851327593401208105741076214120093531")},
                       false};
 }
+
+namespace {
+
+template <class F>
+bool same_point(const Affine<F>& a, const Affine<F>& b) {
+  return a.inf == b.inf && (a.inf || (a.x == b.x && a.y == b.y));
+}
+bool g2_valid(const Affine<HFq2>& p) { return host::g2_on_curve(p) && host::g2_in_subgroup(p); }
 
 // the beacon parameters of a contribution's parameter bytes (1: name, 2: numIterationsExp, one value
 // byte, 3: beacon hash), every length bounded by the bytes present
@@ -805,6 +806,275 @@ bool zkey_verify_frominit(int device, const uint8_t* init, size_t init_len, cons
     // e(sum r_i old_i, delta2) == e(sum r_i new_i, delta2_init)
     if (!same_ratio(host::jac_to_aff(r.sum_a), host::jac_to_aff(r.sum_b), h.delta2, h0.delta2))
       return bad("INVALID: " + name + " section is not the initial one times delta^-1");
+  }
+  return verdict(true, "OK");
+}
+
+// ---------------------------------------------------------------- powersoftau verify: section 7
+// The contribution records of a ptau and their chain (ptau_verify.hpp).  The record layout and the hashes
+// are recalled from snarkjs 0.4.22 (powersoftau_utils.js, powersoftau_verify.js; restated, parity
+// unpinned: no snarkjs-written ptau exists here); the restatement this must equal is
+// tests/helpers/ptau_model.py.  Record: tauG1, tauG2, alphaG1, betaG1, betaG2 (LEM), the key's nine points
+// (tau / alpha / beta g1_s, g1_sx, then the three g2_spx), partialHash (216), nextChallenge (64), type
+// (u32), parameter length (u32) and parameters as in section 10 of a zkey.
+Blake2b Blake2b::resume(const uint8_t state[216]) {
+  auto rd64 = [&](size_t at) {
+    uint64_t v = 0;
+    for (int b = 7; b >= 0; --b) v = (v << 8) | state[at + b];
+    return v;
+  };
+  Blake2b h;
+  for (int i = 0; i < 8; ++i) h.h_[i] = rd64(8 * i);
+  h.t_[0] = rd64(64), h.t_[1] = 0;
+  const uint64_t f = rd64(72), fill = rd64(208);
+  if (f != 0 || fill > 128) throw ZkpError(ZKP_ERR_FORMAT, "Blake2b state: final flag set or buffer fill above 128");
+  std::memcpy(h.buf_, state + 80, 128);
+  h.n_ = (size_t)fill;
+  return h;
+}
+
+namespace {
+
+struct PtauKey {
+  Affine<HFq> g1_s, g1_sx;
+  Affine<HFq2> g2_spx;
+};
+struct PtauContribution {
+  Affine<HFq> tau_g1, alpha_g1, beta_g1;
+  Affine<HFq2> tau_g2, beta_g2;
+  PtauKey key[3];  // tau, alpha, beta
+  uint8_t points_lem[448];  // the five points as the record holds them
+  uint8_t next_challenge[64], response_hash[64];
+  uint32_t type = 0;
+  BeaconParams beacon;
+};
+const char* const KEY_NAME[3] = {"tau", "alpha", "beta"};
+
+std::vector<PtauContribution> read_ptau_contributions(const uint8_t* sec, size_t len) {
+  auto cut = [](const std::string& what) { return ZkpError(ZKP_ERR_FORMAT, "ptau: section 7 " + what); };
+  if (len < 4) throw cut("has no contribution count");
+  const uint32_t n = rd32(sec);
+  size_t o = 4;
+  std::vector<PtauContribution> out;
+  for (uint32_t i = 0; i < n; ++i) {
+    const std::string tag = "contribution " + std::to_string(i);
+    if (len - o < 1504) throw cut(tag + " is truncated");
+    PtauContribution c;
+    try {
+      const uint8_t* p = sec + o;
+      std::memcpy(c.points_lem, p, 448);
+      c.tau_g1 = g1_lem(p), c.tau_g2 = g2_lem(p + 64), c.alpha_g1 = g1_lem(p + 192), c.beta_g1 = g1_lem(p + 256);
+      c.beta_g2 = g2_lem(p + 320);
+      p += 448;
+      for (int k = 0; k < 3; ++k) {
+        c.key[k].g1_s = g1_lem(p + 128 * k), c.key[k].g1_sx = g1_lem(p + 128 * k + 64);
+        c.key[k].g2_spx = g2_lem(p + 384 + 128 * k);
+      }
+    } catch (const ZkpError&) {
+      throw cut(tag + " has a coordinate out of range");
+    }
+    o += 448 + 768;
+    {  // responseHash: the resumed state, then the key's nine points uncompressed
+      Blake2b h = [&] {
+        try {
+          return Blake2b::resume(sec + o);
+        } catch (const ZkpError&) {
+          throw cut(tag + " has a malformed partialHash");
+        }
+      }();
+      for (int k = 0; k < 3; ++k) hash_g1(h, c.key[k].g1_s), hash_g1(h, c.key[k].g1_sx);
+      for (int k = 0; k < 3; ++k) hash_g2(h, c.key[k].g2_spx);
+      h.final(c.response_hash);
+    }
+    o += 216;
+    std::memcpy(c.next_challenge, sec + o, 64);
+    o += 64;
+    c.type = rd32(sec + o);
+    const uint32_t plen = rd32(sec + o + 4);
+    o += 8;
+    if (len - o < plen) throw cut(tag + ": the parameter length runs past the section's end");
+    try {
+      c.beacon = parse_contribution_params(std::vector<uint8_t>(sec + o, sec + o + plen));
+    } catch (const ZkpError&) {
+      throw cut(tag + " has malformed parameters");
+    }
+    o += plen;
+    if (c.type > 1) throw cut(tag + " has an unknown type");
+    if (c.type == 1) {
+      if (!c.beacon.has_exp || !c.beacon.has_hash) throw cut(tag + " is a beacon without beacon parameters");
+      if (c.beacon.exp > 63) throw cut(tag + ": beacon numIterationsExp must be <= 63");
+    }
+    out.push_back(std::move(c));
+  }
+  if (o != len) throw cut("has trailing bytes");
+  return out;
+}
+
+// Blake2b over Blake2b(""), then the sections of a new ceremony of power cp, all generators, uncompressed
+void first_challenge(uint32_t cp, uint8_t out[64]) {
+  Blake2b h;
+  {
+    uint8_t empty[64];
+    Blake2b().final(empty);
+    h.update(empty, 64);
+  }
+  constexpr size_t REP = 512;
+  std::vector<uint8_t> b1(REP * 64), b2(REP * 128);
+  g1_u(Affine<HFq>{fq_small(1), fq_small(2), false}, b1.data());
+  g2_u(g2_generator(), b2.data());
+  for (size_t i = 1; i < REP; ++i) std::memcpy(&b1[i * 64], &b1[0], 64), std::memcpy(&b2[i * 128], &b2[0], 128);
+  auto many = [&](const std::vector<uint8_t>& blk, size_t pb, uint64_t count) {
+    for (uint64_t at = 0; at < count; at += REP) h.update(blk.data(), (size_t)std::min<uint64_t>(REP, count - at) * pb);
+  };
+  const uint64_t N = uint64_t(1) << cp;
+  many(b1, 64, 2 * N - 1), many(b2, 128, N), many(b1, 64, N), many(b1, 64, N), many(b2, 128, 1);
+  h.final(out);
+}
+
+// what a contribution is checked against: the five points and the challenge it answers
+struct PtauPrev {
+  Affine<HFq> tau_g1, alpha_g1, beta_g1;
+  Affine<HFq2> tau_g2, beta_g2;
+  const uint8_t* next_challenge;
+};
+
+Affine<HFq2> key_g2_sp(int k, const uint8_t* challenge, const Affine<HFq>& g1_s, const Affine<HFq>& g1_sx) {
+  Blake2b h;
+  const uint8_t tag = (uint8_t)k;
+  h.update(&tag, 1);
+  h.update(challenge, 64);
+  hash_g1(h, g1_s), hash_g1(h, g1_sx);
+  uint8_t d[64];
+  h.final(d);
+  return hash_to_g2(d);
+}
+
+// "" if contribution i follows prev, else the message
+std::string check_ptau_contribution(size_t i, const PtauContribution& c, const PtauPrev& prev) {
+  const std::string tag = "contribution " + std::to_string(i) + ": ";
+  bool g1_ok = host::g1_on_curve(c.tau_g1) && host::g1_on_curve(c.alpha_g1) && host::g1_on_curve(c.beta_g1);
+  bool g2_ok = g2_valid(c.tau_g2) && g2_valid(c.beta_g2);
+  for (int k = 0; k < 3; ++k) {
+    g1_ok = g1_ok && host::g1_on_curve(c.key[k].g1_s) && host::g1_on_curve(c.key[k].g1_sx);
+    g2_ok = g2_ok && g2_valid(c.key[k].g2_spx);
+  }
+  if (!g1_ok) return tag + "a G1 point is not on the curve";
+  if (!g2_ok) return tag + "a G2 point is not in G2";
+  if (c.type == 1) {
+    uint8_t bh[32];
+    beacon_hash(c.beacon.hash.data(), c.beacon.hash.size(), c.beacon.exp, bh);
+    uint32_t seed[8];
+    seed_from_hash(bh, seed);
+    ChaChaRng rng(seed);
+    U256 prv[3];
+    for (int k = 0; k < 3; ++k) prv[k] = fr_from_rng(rng).to_std();
+    for (int k = 0; k < 3; ++k) {
+      const Affine<HFq> g1_s = g1_from_rng(rng), g1_sx = g1_times(g1_s, prv[k]);
+      const Affine<HFq2> g2_spx = g2_times(key_g2_sp(k, prev.next_challenge, g1_s, g1_sx), prv[k]);
+      auto wrong = [&](const char* what) {
+        return std::string("BEACON key (") + KEY_NAME[k] + what + ") is not generated correctly";
+      };
+      if (!same_point(g1_s, c.key[k].g1_s)) return wrong("G1_s");
+      if (!same_point(g1_sx, c.key[k].g1_sx)) return wrong("G1_sx");
+      if (!same_point(g2_spx, c.key[k].g2_spx)) return wrong("G2_spx");
+    }
+  }
+  Affine<HFq2> g2_sp[3];
+  for (int k = 0; k < 3; ++k) {
+    g2_sp[k] = key_g2_sp(k, prev.next_challenge, c.key[k].g1_s, c.key[k].g1_sx);
+    if (!same_ratio(c.key[k].g1_s, c.key[k].g1_sx, g2_sp[k], c.key[k].g2_spx))
+      return std::string("INVALID key (") + KEY_NAME[k] + ")";
+  }
+  if (!same_ratio(prev.tau_g1, c.tau_g1, g2_sp[0], c.key[0].g2_spx)) return "INVALID tau*G1. contribution";
+  if (!same_ratio(c.key[0].g1_s, c.key[0].g1_sx, prev.tau_g2, c.tau_g2)) return "INVALID tau*G2. contribution";
+  if (!same_ratio(prev.alpha_g1, c.alpha_g1, g2_sp[1], c.key[1].g2_spx)) return "INVALID alpha*G1. contribution";
+  if (!same_ratio(prev.beta_g1, c.beta_g1, g2_sp[2], c.key[2].g2_spx)) return "INVALID beta*G1. contribution";
+  if (!same_ratio(c.key[2].g1_s, c.key[2].g1_sx, prev.beta_g2, c.beta_g2)) return "INVALID beta*G2. contribution";
+  return "";
+}
+
+}  // namespace
+
+bool ptau_verify(int device, const uint8_t* ptau, size_t len, const uint8_t* seed32, std::string& msg) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  ptau_verify_timings() = PtauVerifyTimings{};
+  const PtauFile f = parse_ptau(ptau, len);
+  const std::vector<PtauContribution> cs = read_ptau_contributions(f.sec[7].ptr, f.sec[7].len);
+  // the first challenge (384 * 2^ceremonyPower bytes of hashing: ~100 GB at 28) on a thread of its own,
+  // beside everything up to the first contribution's check, which alone needs it
+  uint8_t first[64];
+  double first_ms = 0, contrib_ms = 0, next_ms = 0;
+  std::thread first_thread;
+  struct Joiner {
+    std::thread& t;
+    ~Joiner() {
+      if (t.joinable()) t.join();
+    }
+  } joiner{first_thread};
+  auto verdict = [&](bool ok, const std::string& m) {
+    if (first_thread.joinable()) first_thread.join();
+    msg = m;
+    PtauVerifyTimings& t = ptau_verify_timings();
+    t.contributions_ms = contrib_ms, t.first_challenge_ms = first_ms, t.next_challenge_ms = next_ms;
+    t.total_ms = ms_since(t_begin);
+    return ok;
+  };
+  if (cs.empty()) return verdict(false, "This file has no contribution! It cannot be used in production");
+  first_thread = std::thread([&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    first_challenge(f.ceremony_power, first);
+    first_ms = ms_since(t0);
+  });
+  const Affine<HFq> g1gen{fq_small(1), fq_small(2), false};
+  const Affine<HFq2> g2gen = g2_generator();
+  auto check = [&](size_t i) {
+    const auto t0 = std::chrono::steady_clock::now();
+    PtauPrev prev;
+    if (i == 0) {
+      if (first_thread.joinable()) first_thread.join();
+      prev = PtauPrev{g1gen, g1gen, g1gen, g2gen, g2gen, first};
+    } else {
+      const PtauContribution& p = cs[i - 1];
+      prev = PtauPrev{p.tau_g1, p.alpha_g1, p.beta_g1, p.tau_g2, p.beta_g2, p.next_challenge};
+    }
+    const std::string m = check_ptau_contribution(i, cs[i], prev);
+    contrib_ms += ms_since(t0);
+    return m;
+  };
+  // the last contribution, its ties to the sections, the sections, the next challenge, then the earlier
+  // contributions from the last but one down, as snarkjs orders them
+  const PtauContribution& last = cs.back();
+  std::string m = check(cs.size() - 1);
+  if (!m.empty()) return verdict(false, m);
+  if (std::memcmp(f.sec[2].ptr + 64, last.points_lem, 64) != 0)
+    return verdict(false, "Second element of tau*G1 section does not match the one in the contribution section");
+  if (std::memcmp(f.sec[3].ptr + 128, last.points_lem + 64, 128) != 0)
+    return verdict(false, "Second element of tau*G2 section does not match the one in the contribution section");
+  if (std::memcmp(f.sec[4].ptr, last.points_lem + 192, 64) != 0)
+    return verdict(false, "First element of alpha*tau*G1 section does not match the one in the contribution section");
+  if (std::memcmp(f.sec[5].ptr, last.points_lem + 256, 64) != 0)
+    return verdict(false, "First element of beta*tau*G1 section does not match the one in the contribution section");
+  if (std::memcmp(f.sec[6].ptr, last.points_lem + 320, 128) != 0)
+    return verdict(false, "beta*G2 does not match the one in the contribution section");
+  if (!ptau_verify_sections(device, ptau, len, seed32, m)) return verdict(false, m);
+  if (f.power == f.ceremony_power) {
+    const auto t0 = std::chrono::steady_clock::now();
+    Blake2b h;
+    h.update(last.response_hash, 64);
+    hash_points<64>(h, f.sec[2].ptr, f.points(2));
+    hash_points<128>(h, f.sec[3].ptr, f.points(3));
+    hash_points<64>(h, f.sec[4].ptr, f.points(4));
+    hash_points<64>(h, f.sec[5].ptr, f.points(5));
+    hash_points<128>(h, f.sec[6].ptr, 1);
+    uint8_t d[64];
+    h.final(d);
+    next_ms = ms_since(t0);
+    if (std::memcmp(d, last.next_challenge, 64) != 0)
+      return verdict(false, "Hash of the values does not match the next challenge of the last contributor in the contributions section");
+  }
+  for (size_t i = cs.size() - 1; i-- > 0;) {
+    m = check(i);
+    if (!m.empty()) return verdict(false, m);
   }
   return verdict(true, "OK");
 }

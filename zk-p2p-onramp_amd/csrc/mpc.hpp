@@ -22,6 +22,10 @@ class Blake2b {
   Blake2b();
   void update(const void* data, size_t len);
   void final(uint8_t out[64]);
+  // A hash in progress from its 216 exported bytes (the partialHash of a ptau contribution): h[8] (u64 LE
+  // each), the bytes compressed so far t (u64), the final flag f (u64, must be 0), the 128-byte buffer and
+  // its fill (u64, <= 128).  Throws ZkpError(ZKP_ERR_FORMAT) on an f or a fill out of range.
+  static Blake2b resume(const uint8_t state[216]);
 
  private:
   void compress(bool last);
@@ -68,6 +72,11 @@ void mpc_contribute(MpcParams& m, ChaChaRng& rng, const host::Affine<host::Fq>& 
 // csHash of a new key (`zkey new`): over its header points and point sections (key bytes, zkey
 // layout) and the H points (tau^(n+i) - tau^i) G1 from the ptau's tauG1 (LEM, >= 2n points)
 void mpc_cs_hash_new(const uint8_t* zkey, size_t len, const uint8_t* tau_g1, size_t tau_g1_points, uint8_t out[64]);
+
+// e(g1a, g2b) == e(g1b, g2a); false if any point is the point at infinity
+bool same_ratio(const host::Affine<host::Fq>& g1a, const host::Affine<host::Fq>& g1b, const host::Affine<host::Fq2>& g2a,
+                const host::Affine<host::Fq2>& g2b);
+host::Affine<host::Fq2> g2_generator();  // Verifier.sol:33-36
 
 // replace (or append) section `id` of a binfile held in `file`
 void binfile_replace_section(std::vector<uint8_t>& file, uint32_t id, const std::vector<uint8_t>& payload);

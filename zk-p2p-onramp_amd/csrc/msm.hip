@@ -292,6 +292,13 @@ MsmBases::MsmBases(Curve curve, size_t n, int c, int depth) : curve_(curve), n_(
   d_ = DevBuf<>(bytes_ / 4);
 }
 
+MsmBases::MsmBases(Curve curve, const uint32_t* points, size_t n, int c)
+    : curve_(curve), n_(n), c_(c), depth_(1), view_(points) {
+  if (c < 2 || !points) throw std::runtime_error("MsmBases: bad parameters");
+  if (std::max<size_t>(n, 1) >= (size_t(1) << 31))
+    throw std::runtime_error("MsmBases: depth * n must stay below 2^31 (31-bit base indices)");
+}
+
 namespace {
 
 // the count of a mask just enqueued on st comes to the host; a mask with every bit set is dropped,
@@ -323,6 +330,7 @@ void settle_mask(BaseMask& m, const uint32_t* d_count, size_t n, hipStream_t st)
 }  // namespace
 
 void MsmBases::extend(hipStream_t st) {
+  if (view_) throw std::runtime_error("MsmBases: a view has no rows to derive");
   mask_ = BaseMask{};
   if (n_ == 0) return;
   mask_.bits = DevBuf<>((n_ + 31) / 32);

@@ -143,6 +143,10 @@ struct BaseMask {
 class MsmBases {
  public:
   MsmBases(Curve curve, size_t n, int c, int depth);
+  // a view, not a table: n points that already lie in HBM in device layout, depth 1, nothing owned and
+  // no mask (a base at infinity costs its lane an addition).  Lets one resident array serve base sets
+  // that overlap (ptau_verify.hip: points [k, k + m) and [k + 1, k + m + 1) under one plan).
+  MsmBases(Curve curve, const uint32_t* points, size_t n, int c);
   // row 0 (n points): the caller fills it (device layout), then extend() derives rows 1..T-1 and the
   // mask of the finite bases from row 0 (it waits for the stream once: the count comes to the host)
   uint32_t* row0() { return d_; }
@@ -151,7 +155,7 @@ class MsmBases {
   const uint32_t* present() const { return mask_.data(); }
   const uint32_t* present_index() const { return mask_.list(); }
   size_t present_count() const { return mask_.bits ? mask_.count : n_; }
-  const uint32_t* data() const { return d_; }
+  const uint32_t* data() const { return view_ ? view_ : d_.get(); }
   size_t n() const { return n_; }
   int c() const { return c_; }
   int depth() const { return depth_; }
@@ -167,6 +171,7 @@ class MsmBases {
   int c_, depth_;
   size_t bytes_ = 0;
   DevBuf<> d_;
+  const uint32_t* view_ = nullptr;
   BaseMask mask_;
 };
 

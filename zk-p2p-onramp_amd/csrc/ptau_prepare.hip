@@ -37,6 +37,7 @@
 #include "hip_raii.hpp"
 #include "host_ec.hpp"
 #include "prover.hpp"
+#include "spans.hpp"
 #include "zkey_verify.hpp"
 
 namespace zkp {
@@ -107,28 +108,6 @@ double wall_ms(std::chrono::steady_clock::time_point t0) {
 }
 
 thread_local PrepareTimings g_timings;
-
-// device ms between pairs of events, read once everything is complete
-struct Spans {
-  std::vector<Event> ev;
-  std::vector<double*> into;
-  void begin(hipStream_t st) {
-    ev.emplace_back(true);
-    HIPX(hipEventRecord(ev.back(), st));
-  }
-  void end(hipStream_t st, double* sum) {
-    ev.emplace_back(true);
-    HIPX(hipEventRecord(ev.back(), st));
-    into.push_back(sum);
-  }
-  void collect() {
-    for (size_t i = 0; i < into.size(); ++i) {
-      float ms;
-      HIPX(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
-      *into[i] += ms;
-    }
-  }
-};
 
 // words of XYZZ work space for nvec vectors of levels up to `power` (none if every level is small)
 template <class F>

@@ -153,6 +153,12 @@ void check_index_range(uint64_t first_index, size_t n) {
     throw ZkpError(ZKP_ERR_INVALID_ARG, "rlc: coefficient index out of range");
 }
 
+double wall_ms(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
 // window bits for n uniform 128-bit scalars at depth 1: lg n - 3 as the kernel-level MSMs take, moved
 // off the widths whose top window (128 - (W - 1) c bits) collapses into a few buckets of one group
 // (dense_window_bits states the cost for 254-bit scalars)
@@ -168,12 +174,6 @@ int rlc_window_bits(size_t n) {
   }
   return c;
 }
-
-double wall_ms(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-}  // namespace
 
 size_t verify_chunk_points() {
   constexpr size_t DEFAULT = size_t(1) << 22, MAX = size_t(1) << 24;
@@ -205,6 +205,14 @@ void rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_index, size_t 
     HIPX(hipStreamSynchronize(st));
     for (size_t i = 0; i < m; ++i) std::memcpy(out + (at + i) * 16, h.data() + i * 8, 16);
   }
+}
+
+void rlc_coeffs_resident(const uint8_t* seed32, uint64_t first_index, size_t n, uint32_t* d_out, hipStream_t st) {
+  check_index_range(first_index, n);
+  if (!n) return;
+  const uint64_t blocks = ((first_index + n - 1) >> 2) - (first_index >> 2) + 1;
+  hipLaunchKernelGGL(k_rlc_coeffs, dim3(grid(blocks)), dim3(TPB), 0, st, seed_words(seed32), first_index, (uint64_t)n, d_out);
+  HIPX(hipGetLastError());
 }
 
 void points_check(int device, bool g2, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad) {

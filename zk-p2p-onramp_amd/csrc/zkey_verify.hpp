@@ -55,6 +55,11 @@ size_t verify_chunk_points();
 // coefficient i = the 128-bit LE integer of words 4i..4i+3 of ChaChaRng(seed_from_hash(seed32));
 // out: n x 16 bytes LE (generated on the device)
 void rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_index, size_t n, uint8_t* out);
+// coefficients first_index .. first_index + n - 1 as 8-word scalars (upper four words zero) into d_out
+// (device, n x 8 words), queued on st
+void rlc_coeffs_resident(const uint8_t* seed32, uint64_t first_index, size_t n, uint32_t* d_out, hipStream_t st);
+// window bits of a depth-1 plan over n uniform 128-bit scalars (scalar_bits = 129)
+int rlc_window_bits(size_t n);
 // zkey-layout points (G1 64 bytes, G2 128): *n_bad of them are not canonical (a coordinate >= p) or
 // neither all-zero nor on the curve; *first_bad: the smallest such index (RLC_NO_BAD if none)
 void points_check(int device, bool g2, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad);

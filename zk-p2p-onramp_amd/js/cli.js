@@ -16,9 +16,12 @@
  *   node cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>
  * and the last step of phase 1 (reference circuit/scripts/generate_keys_phase1.sh:20), whose output `zkey new` reads:
  *   node cli.js powersoftau prepare phase2 <pot_beacon.ptau> <pot_final.ptau> [-v]
+ * and the check of a phase-1 file (reference circuit/scripts/generate_keys_phase1.sh:16; the step
+ * generate_keys_phase2_groth16.sh:3 comments out as too slow):
+ *   node cli.js powersoftau verify <pot.ptau> [-v]
  */
 const fs = require('fs');
-const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, release } = require('./groth16');
+const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, powersOfTau, release } = require('./groth16');
 
 const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n' +
               '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
@@ -26,7 +29,8 @@ const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.
               '       cli.js zkey contribute <in.zkey> <out.zkey> -e=<entropy> [-n=name]\n' +
               '       cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]\n' +
               '       cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n' +
-              '       cli.js powersoftau prepare phase2 <in.ptau> <out.ptau> [-v]\n';
+              '       cli.js powersoftau prepare phase2 <in.ptau> <out.ptau> [-v]\n' +
+              '       cli.js powersoftau verify <pot.ptau> [-v]\n';
 
 async function main(argv) {
   if (argv.length === 5 && argv[0] === 'zkey' && argv[1] === 'export' && argv[2] === 'soliditycalldata') {
@@ -44,6 +48,15 @@ async function main(argv) {
   if (named.length === 5 && argv[0] === 'powersoftau' && argv[1] === 'prepare' && argv[2] === 'phase2') {
     await preparePhase2(named[3], named[4]);
     return 0;
+  }
+  if (named.length === 3 && argv[0] === 'powersoftau' && argv[1] === 'verify') {
+    // snarkjs' log lines (recalled from snarkjs 0.4.22, unpinned): "[INFO]  snarkJS: Powers Of tau file OK!" and
+    // exit 0, else the reason and "[ERROR] snarkJS: Invalid ptau" and exit 1
+    const logger = {
+      info: (m) => process.stdout.write(`[INFO]  snarkJS: ${m}\n`),
+      error: (m) => process.stdout.write(`[ERROR] snarkJS: ${m}\n`),
+    };
+    return (await powersOfTau.verify(named[2], logger)) ? 0 : 1;
   }
   if (named.length === 5 && argv[0] === 'zkey' && argv[1] === 'verify') {
     // snarkjs' log lines (recalled from snarkjs 0.4.22, unpinned): "[INFO]  snarkJS: ZKey Ok!" and exit 0,

@@ -262,6 +262,25 @@ async function verifyFromInit(initName, zkeyName, logger, device, ...rest) {
   return reportVerdict(addon.zkeyVerify(readInput(initName), readInput(zkeyName), device || 0), logger);
 }
 
+/*
+ * snarkjs' `powersOfTau.verify(tauFilename, logger)` (the `powersoftau verify` step, reference
+ * circuit/scripts/generate_keys_phase1.sh:16; skipped as too slow in generate_keys_phase2_groth16.sh:3): the
+ * contribution chain on the host, every point section on the GPU.  Resolves to a boolean; the failing check
+ * goes to logger.error, "Powers Of tau file OK!" to logger.info (strings recalled from snarkjs 0.4.22,
+ * unpinned).  Malformed input rejects.
+ */
+async function verifyPtau(ptauName, logger, device) {
+  const res = addon.ptauVerify(readInput(ptauName), device || 0);
+  if (logger) {
+    if (res.valid && logger.info) logger.info('Powers Of tau file OK!');
+    if (!res.valid && logger.error) {
+      logger.error(res.message);
+      logger.error('Invalid ptau');
+    }
+  }
+  return res.valid;
+}
+
 function release() {
   for (const h of provers.values()) addon.freeProver(h);
   for (const h of memProvers.values()) addon.freeProver(h);
@@ -273,7 +292,7 @@ module.exports = {
   groth16: { prove, proveBatch },
   proveBatch,
   zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit },
-  powersOfTau: { preparePhase2 },
+  powersOfTau: { preparePhase2, verify: verifyPtau },
   preparePhase2,
   verifyFromR1cs,
   verifyFromInit,

@@ -42,6 +42,9 @@ export declare const powersOfTau: {
    *  `zkey new` reads); writes newPtauName when given, returns the file's bytes */
   preparePhase2(oldPtauName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array }, logger?: Logger,
                 device?: number): Promise<Buffer>;
+  /** `snarkjs powersoftau verify` (zkp_ptau_verify): the contribution chain on the host, every point section
+   *  on the GPU; resolves to the verdict, the failing check goes to logger.error */
+  verify(ptauName: Input, logger?: VerifyLogger, device?: number): Promise<boolean>;
 };
 export declare function preparePhase2(oldPtauName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array },
                                       logger?: Logger, device?: number): Promise<Buffer>;

@@ -14,6 +14,7 @@
  *   zkeyBeacon(zkeyBuffer, beaconBuffer, numIterationsExp, device?, name?) -> Buffer (`zkey beacon`)
  *   zkeyContribute(zkeyBuffer, entropy, name?, device?) -> Buffer (`zkey contribute`)
  *   zkeyVerify(initBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify` against the initial key)
+ *   ptauVerify(ptauBuffer, device?)            -> {valid, message} (`snarkjs powersoftau verify`, synchronous)
  *   zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify`)
  *   version()
  * prove()/proveBatch() run on the libuv threadpool (napi_async_work), so the JS main
@@ -156,7 +157,8 @@ static napi_value js_ptau_prepare_phase2(napi_env env, napi_callback_info info) 
 /* zkeyVerify(initBuffer, zkeyBuffer, device?) / zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer,
  * device?) -> {valid: boolean, message: string}: `snarkjs zkey verify` (zkp_zkey_verify_frominit /
  * zkp_zkey_verify, coefficients seeded by the OS CSPRNG), synchronous -- a setup step.  Malformed
- * input throws with the zkp_status as code. */
+ * input throws with the zkp_status as code.  ptauVerify(ptauBuffer, device?): the same shape for
+ * `snarkjs powersoftau verify` (zkp_ptau_verify). */
 static napi_value verify_common(napi_env env, napi_callback_info info, int nbuf, const char* usage) {
   size_t argc = 4;
   napi_value argv[4];
@@ -178,7 +180,8 @@ static napi_value verify_common(napi_env env, napi_callback_info info, int nbuf,
   int valid = 0;
   char msg[256];
   zkp_status st =
-      nbuf == 2 ? zkp_zkey_verify_frominit(device, (const uint8_t*)p[0], len[0], (const uint8_t*)p[1], len[1], NULL,
+      nbuf == 1 ? zkp_ptau_verify(device, (const uint8_t*)p[0], len[0], NULL, &valid, msg, sizeof msg)
+      : nbuf == 2 ? zkp_zkey_verify_frominit(device, (const uint8_t*)p[0], len[0], (const uint8_t*)p[1], len[1], NULL,
                                            &valid, msg, sizeof msg)
                 : zkp_zkey_verify(device, (const uint8_t*)p[0], len[0], (const uint8_t*)p[1], len[1],
                                   (const uint8_t*)p[2], len[2], NULL, &valid, msg, sizeof msg);
@@ -193,6 +196,9 @@ static napi_value verify_common(napi_env env, napi_callback_info info, int nbuf,
 }
 static napi_value js_zkey_verify(napi_env env, napi_callback_info info) {
   return verify_common(env, info, 2, "zkeyVerify(initBuffer, zkeyBuffer, device?)");
+}
+static napi_value js_ptau_verify(napi_env env, napi_callback_info info) {
+  return verify_common(env, info, 1, "ptauVerify(ptauBuffer, device?)");
 }
 static napi_value js_zkey_verify_r1cs(napi_env env, napi_callback_info info) {
   return verify_common(env, info, 3, "zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?)");
@@ -678,6 +684,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"zkeyBeacon", NULL, js_zkey_beacon, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyContribute", NULL, js_zkey_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerify", NULL, js_zkey_verify, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauVerify", NULL, js_ptau_verify, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromR1cs", NULL, js_zkey_verify_r1cs, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);

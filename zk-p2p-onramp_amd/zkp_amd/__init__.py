@@ -161,8 +161,17 @@ def load_library(path: str = LIB_PATH):
             lib.zkp_rlc_coeffs.argtypes = [ctypes.c_int, u8p, ctypes.c_uint64, sz, u8p]
             lib.zkp_points_check.argtypes = [ctypes.c_int, ctypes.c_int, u8p, sz, u64p, u64p]
             lib.zkp_rlc_g1.argtypes = [ctypes.c_int, u8p, ctypes.c_uint64, u8p, u8p, sz, u8p, ip, u8p, ip]
+        if hasattr(lib, "zkp_ptau_verify_sections"):  # powersoftau verify (an older library loads for A/B runs)
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            ip = ctypes.POINTER(ctypes.c_int)
+            lib.zkp_ptau_verify_sections.argtypes = [ctypes.c_int, u8p, sz, u8p, ip, ctypes.c_char_p, sz]
+            lib.zkp_ptau_verify.argtypes = [ctypes.c_int, u8p, sz, u8p, ip, ctypes.c_char_p, sz]
+            lib.zkp_ptau_verify_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+            lib.zkp_g2_subgroup_check.argtypes = [ctypes.c_int, u8p, sz, u64p, u64p]
+            lib.zkp_rlc_pairs.argtypes = [ctypes.c_int, ctypes.c_int, u8p, ctypes.c_uint64, u8p, sz, u8p, ip, u8p, ip]
         for name in ("zkp_zkey_verify_frominit", "zkp_zkey_verify", "zkp_zkey_verify_timings", "zkp_rlc_coeffs",
-                     "zkp_points_check", "zkp_rlc_g1"):
+                     "zkp_points_check", "zkp_rlc_g1", "zkp_ptau_verify", "zkp_ptau_verify_sections", "zkp_ptau_verify_timings",
+                     "zkp_g2_subgroup_check", "zkp_rlc_pairs"):
             if hasattr(lib, name):
                 getattr(lib, name).restype = ctypes.c_int
         for name in ("zkp_zkey_beacon_named", "zkp_zkey_contribute_entropy", "zkp_blake2b512", "zkp_prover_set_verify", "zkp_prover_get_verify", "zkp_proof_verify", "zkp_pairing", "zkp_prover_load_mem", "zkp_prover_load_file", "zkp_prover_info", "zkp_prove",
@@ -770,6 +779,73 @@ def rlc_g1(seed: bytes, first_index: int, points_a: bytes, points_b: bytes, devi
     def pt(raw, inf):
         raw = bytes(raw)
         return None if inf.value else (_le(raw[:32]), _le(raw[32:]))
+    return pt(oa, ia), pt(ob, ib)
+
+
+def ptau_verify_sections(ptau: bytes, seed: bytes = None, device: int = 0):
+    """The point sections of `snarkjs powersoftau verify <ptau>` on the GPU (zkp_ptau_verify_sections):
+    every point of sections 2-6 and 12-15 on its curve, every G2 point in the subgroup, the singular
+    points, the powers and the Lagrange sections -> (valid, message): (True, "OK") or (False, the first
+    failing check).  seed as zkey_verify_frominit (production: None).  A malformed file raises ZkpError."""
+    lib = load_library()
+    pp, plen, pk = _in(ptau)
+    sp, sk = _seed(seed)
+    ok = ctypes.c_int()
+    msg = ctypes.create_string_buffer(VERIFY_MSG_CAP)
+    _check(lib.zkp_ptau_verify_sections(device, pp, plen, sp, ctypes.byref(ok), msg, VERIFY_MSG_CAP))
+    return bool(ok.value), msg.value.decode()
+
+
+def ptau_verify(ptau: bytes, seed: bytes = None, device: int = 0):
+    """`snarkjs powersoftau verify <ptau>` (zkp_ptau_verify): the contribution chain of section 7 on the host
+    and ptau_verify_sections on the GPU -> (valid, message)."""
+    lib = load_library()
+    pp, plen, pk = _in(ptau)
+    sp, sk = _seed(seed)
+    ok = ctypes.c_int()
+    msg = ctypes.create_string_buffer(VERIFY_MSG_CAP)
+    _check(lib.zkp_ptau_verify(device, pp, plen, sp, ctypes.byref(ok), msg, VERIFY_MSG_CAP))
+    return bool(ok.value), msg.value.decode()
+
+
+def ptau_verify_timings() -> dict:
+    """ms of the calling thread's last ptau_verify / ptau_verify_sections (zkp_ptau_verify_timings)."""
+    out = (ctypes.c_double * 17)()
+    _check(load_library().zkp_ptau_verify_timings(out, 17))
+    keys = ["total", "parse", "upload", "point_check", "subgroup_check", "coeff_gen", "ntt_scalar_fold", "plan",
+            "accumulate_pairs", "accumulate_lagrange", "accumulate_tau", "host_fold", "host_pairings", "chunks",
+            "contributions", "first_challenge", "next_challenge"]
+    return dict(zip(keys, list(out)))
+
+
+def g2_subgroup_check(points_lem: bytes, device: int = 0):
+    """Kernel-level: (bad, first_bad) over zkey-layout G2 points on the curve (zkp_g2_subgroup_check): how
+    many are neither all-zero nor of order r, and the smallest such index (None if 0)."""
+    pp, pk = _buf(bytes(points_lem) or b"\0")
+    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(load_library().zkp_g2_subgroup_check(device, pp, len(points_lem) // 128, ctypes.byref(bad),
+                                                ctypes.byref(first)))
+    return bad.value, (first.value if bad.value else None)
+
+
+def rlc_pairs(seed: bytes, first_index: int, points: bytes, g2: bool = False, device: int = 0):
+    """Kernel-level: A = sum_{i<n-1} r_i P_i and B = sum_{i<n-1} r_i P_(i+1) over n zkey-layout points
+    under one MSM plan, r_i = coefficient first_index + i (zkp_rlc_pairs) -> (A, B), each a point
+    ((x, y); G2: ((x0, x1), (y0, y1))) or None for infinity."""
+    pb = 128 if g2 else 64
+    sp, sk = _seed(seed)
+    pp, pk = _buf(bytes(points) or b"\0")
+    oa, ob = (ctypes.c_uint8 * pb)(), (ctypes.c_uint8 * pb)()
+    ia, ib = ctypes.c_int(), ctypes.c_int()
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    _check(load_library().zkp_rlc_pairs(device, 1 if g2 else 0, sp, first_index, pp, len(points) // pb,
+                                        ctypes.cast(oa, u8p), ctypes.byref(ia), ctypes.cast(ob, u8p), ctypes.byref(ib)))
+
+    def pt(raw, inf):
+        v = [_le(bytes(raw)[32 * i:32 * i + 32]) for i in range(pb // 32)]
+        if inf.value:
+            return None
+        return ((v[0], v[1]), (v[2], v[3])) if g2 else (v[0], v[1])
     return pt(oa, ia), pt(ob, ib)
 
 
