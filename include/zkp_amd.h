@@ -441,6 +441,50 @@ zkp_status zkp_bench_ntt(int device, int log_n, int warmup, int iters, double* m
  * launch over all of them: what the prover runs on the quotient's A, B, C */
 zkp_status zkp_bench_ntt_batch(int device, int log_n, int count, int warmup, int iters, double* ms);
 
+/* ---- Phase 1 from its start: `snarkjs powersoftau new | contribute | beacon` (reference
+ * circuit/scripts/generate_keys_phase1.sh:6,8,10,18).  With zkp_ptau_verify and zkp_ptau_prepare_phase2 the
+ * script's commands run here end to end, except `export challenge`, `challenge contribute` and `import
+ * response` (script lines 12-14: the challenge-file format is another restatement, left for later).  The
+ * formats are restated from snarkjs 0.4.22 (parity unpinned); tests/helpers/ptau_model.py fixes them byte for
+ * byte.  Buffers handed out are released with zkp_buffer_free.
+ *
+ * zkp_ptau_new: `powersoftau new bn128 <power>`; host only.  Sections 1-7, every point a generator, no
+ * contribution.  power within 1..28, ceremony_power >= power (0: = power), else ZKP_ERR_INVALID_ARG.
+ *
+ * zkp_ptau_contribute: one contribution on the GPU.  The key comes from the rng that
+ * zkp_zkey_contribute_entropy builds from rand64 (NULL: 64 bytes of the OS CSPRNG) and entropy; it answers the
+ * last record's nextChallenge, or the first challenge of a file without contributions.  tauG1[i] and tauG2[i]
+ * are multiplied by tau^i, alphaTauG1[i] by alpha tau^i, betaTauG1[i] by beta tau^i, betaG2 by beta
+ * (5 * 2^power - 1 scalar multiplications, each point by its own scalar), and a record is appended to section
+ * 7 (name: recorded unless NULL).  Input: sections 1-7 of a bn128 ptau v1 with the sizes its power gives, else
+ * ZKP_ERR_FORMAT / ZKP_ERR_CURVE naming the section, before the device is touched; every point of sections 2-6
+ * canonical and on its curve or all-zero, else ZKP_ERR_FORMAT "ptau: section <id> point <i> is not on the
+ * curve" (checked on the device).  A truncated file (power < ceremonyPower) is refused with
+ * ZKP_ERR_INVALID_ARG: the next challenge hashes the sections of the whole ceremony, which such a file no
+ * longer holds.  Output: sections 1-7 in that order; sections 12-15 of the input are dropped (a contribution
+ * invalidates them) and any other id is not copied.  ZKP_PTAU_CHUNK: points per chunk streamed through the
+ * device (default 4194304; a malformed value or one below 1 is ZKP_ERR_INVALID_ARG).  ZKP_PTAU_WINDOW=1|2: the
+ * window bits of the per-point ladder (default 2, the faster one; the bytes are the same).
+ *
+ * zkp_ptau_beacon: the same with the beacon's rng (zkp_zkey_beacon's), a type-1 record and its two
+ * parameters; num_iterations_exp <= 63 and beacon_len <= 255, else ZKP_ERR_INVALID_ARG.
+ *
+ * zkp_ptau_contribute_timings: ms of the calling thread's last contribute / beacon: [0] total, [1] parse +
+ * point check, [2] first / last challenge, [3] key draw, [4] upload, [5] G1 scaling, [6] G2 scaling,
+ * [7] encoding, [8] download, [9] partial-hash thread, [10] next-challenge thread, [11] chunks.
+ *
+ * zkp_points_scale_powers (kernel-level): out_i = (first * ratio^i) * P_i, i < n; zkey layout in and out
+ * (G1 64 bytes, G2 128; canonical and on the curve or all-zero, else ZKP_ERR_INVALID_ARG); first32 / ratio32
+ * 32-byte LE, reduced mod r. */
+zkp_status zkp_ptau_new(uint32_t power, uint32_t ceremony_power /* 0: = power */, uint8_t** out, size_t* out_len);
+zkp_status zkp_ptau_contribute(int device, const uint8_t* ptau, size_t len, const uint8_t* rand64 /* NULL: OS CSPRNG */,
+                               const char* entropy, const char* name, uint8_t** out, size_t* out_len);
+zkp_status zkp_ptau_beacon(int device, const uint8_t* ptau, size_t len, const uint8_t* beacon, size_t beacon_len,
+                           uint32_t num_iterations_exp, const char* name, uint8_t** out, size_t* out_len);
+zkp_status zkp_ptau_contribute_timings(double* ms, int n);
+zkp_status zkp_points_scale_powers(int device, int g2, const uint8_t* points, size_t n, const uint8_t* first32,
+                                   const uint8_t* ratio32, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

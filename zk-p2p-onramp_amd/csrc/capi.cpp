@@ -25,6 +25,7 @@
 #include "host_pairing.hpp"
 #include "mpc.hpp"
 #include "prover.hpp"
+#include "ptau_contribute.hpp"
 #include "ptau_verify.hpp"
 #include "zkey_io.hpp"
 #include "zkey_verify.hpp"
@@ -259,6 +260,25 @@ zkp_status zkp_beacon_secret(const uint8_t* beacon, size_t len, uint32_t num_ite
 }  // extern "C"
 
 namespace {
+// snarkjs misc.getRandomRng seeded as `contribute -e=<entropy>` seeds it: Blake2b(64 random bytes || entropy)
+zkp::ChaChaRng entropy_rng(const uint8_t* rand64, const char* entropy) {
+  uint8_t rnd[64];
+  if (rand64) {
+    std::memcpy(rnd, rand64, 64);
+  } else {  // 64 bytes from the OS CSPRNG
+    std::ifstream f("/dev/urandom", std::ios::binary);
+    if (!f.read(reinterpret_cast<char*>(rnd), 64)) throw zkp::ZkpError(ZKP_ERR_IO, "cannot read /dev/urandom");
+  }
+  zkp::Blake2b hh;
+  hh.update(rnd, 64);
+  hh.update(entropy, std::strlen(entropy));
+  uint8_t d[64];
+  hh.final(d);
+  uint32_t seed[8];
+  zkp::seed_from_hash(d, seed);
+  return zkp::ChaChaRng(seed);
+}
+
 // one phase-2 contribution drawn from rng: the record appended to section 10 (mpc.cpp), then the
 // group arithmetic on the GPU (delta -> k delta, L and H -> k^-1) and the new section 10
 std::vector<uint8_t> contribute_mpc(int device, const uint8_t* zkey, size_t len, zkp::ChaChaRng& rng, uint32_t type,
@@ -301,21 +321,7 @@ zkp_status zkp_zkey_contribute_entropy(int device, const uint8_t* zkey, size_t l
   if (!zkey || !entropy || !out || !out_len) return fail(ZKP_ERR_INVALID_ARG, "null argument");
   std::vector<uint8_t> buf;
   zkp_status s = guard([&] {
-    uint8_t rnd[64];
-    if (rand64) {
-      std::memcpy(rnd, rand64, 64);
-    } else {  // snarkjs misc.getRandomRng: 64 bytes from the OS CSPRNG
-      std::ifstream f("/dev/urandom", std::ios::binary);
-      if (!f.read(reinterpret_cast<char*>(rnd), 64)) throw zkp::ZkpError(ZKP_ERR_IO, "cannot read /dev/urandom");
-    }
-    zkp::Blake2b hh;
-    hh.update(rnd, 64);
-    hh.update(entropy, std::strlen(entropy));
-    uint8_t d[64];
-    hh.final(d);
-    uint32_t seed[8];
-    zkp::seed_from_hash(d, seed);
-    zkp::ChaChaRng rng(seed);
+    zkp::ChaChaRng rng = entropy_rng(rand64, entropy);
     buf = contribute_mpc(device, zkey, len, rng, 0, name, nullptr, 0, 0);
   });
   return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
@@ -474,6 +480,56 @@ zkp_status zkp_ptau_verify_timings(double* ms, int n) {
                         t.first_challenge_ms, t.next_challenge_ms};
   for (int i = 0; i < n && i < 17; ++i) ms[i] = v[i];
   return ZKP_OK;
+}
+
+zkp_status zkp_ptau_new(uint32_t power, uint32_t ceremony_power, uint8_t** out, size_t* out_len) {
+  if (!out || !out_len) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] { buf = zkp::ptau_new(power, ceremony_power); });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_ptau_contribute(int device, const uint8_t* ptau, size_t len, const uint8_t* rand64, const char* entropy,
+                               const char* name, uint8_t** out, size_t* out_len) {
+  if (!ptau || !len || !entropy || !out || !out_len) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] {
+    zkp::ChaChaRng rng = entropy_rng(rand64, entropy);
+    buf = zkp::ptau_contribute(device, ptau, len, rng, 0, name, nullptr, 0, 0);
+  });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_ptau_beacon(int device, const uint8_t* ptau, size_t len, const uint8_t* beacon, size_t beacon_len,
+                           uint32_t num_iterations_exp, const char* name, uint8_t** out, size_t* out_len) {
+  if (!ptau || !len || (!beacon && beacon_len) || !out || !out_len)
+    return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  if (num_iterations_exp > 63) return fail(ZKP_ERR_INVALID_ARG, "beacon: numIterationsExp must be <= 63");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] {
+    uint8_t h[32];
+    zkp::beacon_hash(beacon, beacon_len, num_iterations_exp, h);
+    uint32_t seed[8];
+    zkp::seed_from_hash(h, seed);
+    zkp::ChaChaRng rng(seed);
+    buf = zkp::ptau_contribute(device, ptau, len, rng, 1, name, beacon, beacon_len, num_iterations_exp);
+  });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_ptau_contribute_timings(double* ms, int n) {
+  if (!ms || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const zkp::PtauContributeTimings t = zkp::ptau_contribute_timings();
+  const double v[12] = {t.total_ms, t.parse_check_ms, t.challenge_ms,  t.key_ms,          t.upload_ms,         t.g1_ms,
+                        t.g2_ms,    t.encode_ms,      t.download_ms,   t.partial_hash_ms, t.next_challenge_ms, (double)t.chunks};
+  for (int i = 0; i < n && i < 12; ++i) ms[i] = v[i];
+  return ZKP_OK;
+}
+
+zkp_status zkp_points_scale_powers(int device, int g2, const uint8_t* points, size_t n, const uint8_t* first32,
+                                   const uint8_t* ratio32, uint8_t* out) {
+  if ((n && (!points || !out)) || !first32 || !ratio32) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::points_scale_powers(device, g2 != 0, points, n, first32, ratio32, out); });
 }
 
 zkp_status zkp_g2_subgroup_check(int device, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad) {

@@ -10,6 +10,7 @@
 #include "beacon.hpp"
 #include "host_pairing.hpp"
 #include "prover.hpp"
+#include "ptau_contribute.hpp"
 #include "ptau_verify.hpp"
 #include "zkey_verify.hpp"
 
@@ -1077,6 +1078,111 @@ bool ptau_verify(int device, const uint8_t* ptau, size_t len, const uint8_t* see
     if (!m.empty()) return verdict(false, m);
   }
   return verdict(true, "OK");
+}
+
+// ---------------------------------------------------------------- powersoftau new / contribute / beacon
+// (ptau_contribute.hpp; the host parts of tests/helpers/ptau_model.py new, draw_key and contribute)
+
+void Blake2b::save(uint8_t state[216]) const {
+  auto wr64 = [&](size_t at, uint64_t v) {
+    for (int b = 0; b < 8; ++b) state[at + b] = (uint8_t)(v >> (8 * b));
+  };
+  for (int i = 0; i < 8; ++i) wr64(8 * i, h_[i]);
+  wr64(64, t_[0]), wr64(72, 0);
+  std::memset(state + 80, 0, 128);
+  std::memcpy(state + 80, buf_, n_);
+  wr64(208, n_);
+}
+
+std::vector<uint8_t> ptau_new(uint32_t power, uint32_t ceremony_power) {
+  if (!ceremony_power) ceremony_power = power;
+  if (power < 1 || power > 28) throw ZkpError(ZKP_ERR_INVALID_ARG, "ptau new: power must be within 1..28");
+  if (ceremony_power < power) throw ZkpError(ZKP_ERR_INVALID_ARG, "ptau new: ceremonyPower below power");
+  const size_t N = (size_t)1 << power;
+  const size_t count[8] = {0, 0, 2 * N - 1, N, N, N, 1, 0};
+  std::vector<uint8_t> g1, g2;
+  put_g1_lem(g1, Affine<HFq>{fq_small(1), fq_small(2), false});
+  put_g2_lem(g2, g2_generator());
+  size_t total = 12 + 12 + 44 + 12 + 4;
+  for (int id = 2; id <= 6; ++id) total += 12 + count[id] * (PtauFile::is_g2(id) ? 128 : 64);
+  std::vector<uint8_t> out(total);
+  uint8_t* o = out.data();
+  auto w32 = [&](uint32_t x) { std::memcpy(o, &x, 4), o += 4; };
+  auto w64 = [&](uint64_t x) { std::memcpy(o, &x, 8), o += 8; };
+  std::memcpy(o, "ptau", 4), o += 4;
+  w32(1), w32(7);
+  w32(1), w64(44), w32(32);
+  std::memcpy(o, host::FQ_DESC.mod.w, 32), o += 32;
+  w32(power), w32(ceremony_power);
+  for (int id = 2; id <= 6; ++id) {
+    const std::vector<uint8_t>& g = PtauFile::is_g2(id) ? g2 : g1;
+    w32((uint32_t)id), w64(count[id] * g.size());
+    for (size_t i = 0; i < count[id]; ++i) std::memcpy(o, g.data(), g.size()), o += g.size();
+  }
+  w32(7), w64(4), w32(0);
+  return out;
+}
+
+PtauDraw ptau_draw(ChaChaRng& rng) {
+  PtauDraw d;
+  for (int k = 0; k < 3; ++k) {
+    const HFr s = fr_from_rng(rng);
+    // Fr.fromRng draws again on a value >= r; it can give 0 only with probability 2^-254
+    if (s.is_zero()) throw ZkpError(ZKP_ERR_INTERNAL, "ptau contribute: zero secret drawn");
+    d.prv[k] = s.to_std();
+  }
+  for (int k = 0; k < 3; ++k) {
+    d.g1_s[k] = g1_from_rng(rng);
+    d.g1_sx[k] = g1_times(d.g1_s[k], d.prv[k]);
+  }
+  return d;
+}
+
+bool ptau_last_challenge(const uint8_t* sec7, size_t len, uint8_t out[64]) {
+  const std::vector<PtauContribution> cs = read_ptau_contributions(sec7, len);
+  if (cs.empty()) return false;
+  std::memcpy(out, cs.back().next_challenge, 64);
+  return true;
+}
+
+void ptau_first_challenge(uint32_t ceremony_power, uint8_t out[64]) { first_challenge(ceremony_power, out); }
+
+std::vector<uint8_t> ptau_record(const PtauDraw& d, const uint8_t challenge[64], const uint8_t points_lem[448],
+                                 const Blake2b& partial, uint32_t type, const char* name, const uint8_t* beacon,
+                                 size_t beacon_len, uint32_t num_iterations_exp, uint8_t response_hash[64]) {
+  std::vector<uint8_t> rec(points_lem, points_lem + 448);
+  Affine<HFq2> g2_spx[3];
+  for (int k = 0; k < 3; ++k) {
+    g2_spx[k] = g2_times(key_g2_sp(k, challenge, d.g1_s[k], d.g1_sx[k]), d.prv[k]);
+    put_g1_lem(rec, d.g1_s[k]), put_g1_lem(rec, d.g1_sx[k]);
+  }
+  for (int k = 0; k < 3; ++k) put_g2_lem(rec, g2_spx[k]);
+  uint8_t state[216];
+  partial.save(state);
+  rec.insert(rec.end(), state, state + 216);
+  Blake2b h = partial;
+  for (int k = 0; k < 3; ++k) hash_g1(h, d.g1_s[k]), hash_g1(h, d.g1_sx[k]);
+  for (int k = 0; k < 3; ++k) hash_g2(h, g2_spx[k]);
+  h.final(response_hash);
+  rec.insert(rec.end(), 64, 0);  // nextChallenge: the caller's, once the uncompressed sections are hashed
+  std::vector<uint8_t> prm;
+  if (name) {
+    const std::string nm = mpc_name_utf8(name);
+    prm.push_back(1);
+    prm.push_back((uint8_t)nm.size());
+    prm.insert(prm.end(), nm.begin(), nm.end());
+  }
+  if (type == 1) {
+    if (beacon_len > 255 || num_iterations_exp > 255) throw ZkpError(ZKP_ERR_INVALID_ARG, "beacon: parameter too long");
+    prm.push_back(2);
+    prm.push_back((uint8_t)num_iterations_exp);
+    prm.push_back(3);
+    prm.push_back((uint8_t)beacon_len);
+    prm.insert(prm.end(), beacon, beacon + beacon_len);
+  }
+  put32(rec, type), put32(rec, (uint32_t)prm.size());
+  rec.insert(rec.end(), prm.begin(), prm.end());
+  return rec;
 }
 
 }  // namespace zkp

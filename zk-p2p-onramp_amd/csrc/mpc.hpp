@@ -26,6 +26,8 @@ class Blake2b {
   // each), the bytes compressed so far t (u64), the final flag f (u64, must be 0), the 128-byte buffer and
   // its fill (u64, <= 128).  Throws ZkpError(ZKP_ERR_FORMAT) on an f or a fill out of range.
   static Blake2b resume(const uint8_t state[216]);
+  // the same 216 bytes of this hash in progress (f = 0): resume(save()) continues it
+  void save(uint8_t state[216]) const;
 
  private:
   void compress(bool last);

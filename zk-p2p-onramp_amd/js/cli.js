@@ -19,6 +19,11 @@
  * and the check of a phase-1 file (reference circuit/scripts/generate_keys_phase1.sh:16; the step
  * generate_keys_phase2_groth16.sh:3 comments out as too slow):
  *   node cli.js powersoftau verify <pot.ptau> [-v]
+ * and phase 1 from its start (reference circuit/scripts/generate_keys_phase1.sh:6,8,10,18):
+ *   node cli.js powersoftau new bn128 <power> <out.ptau> [-v]
+ *   node cli.js powersoftau contribute <in.ptau> <out.ptau> [--name=|-n=name] [-e=entropy] [-v]
+ *   node cli.js powersoftau beacon <in.ptau> <out.ptau> <beaconHashHex> <numIterationsExp> [-n=name] [-v]
+ * (`export challenge`, `challenge contribute` and `import response`, script lines 12-14, are not implemented)
  */
 const fs = require('fs');
 const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, powersOfTau, release } = require('./groth16');
@@ -30,7 +35,10 @@ const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.
               '       cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]\n' +
               '       cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n' +
               '       cli.js powersoftau prepare phase2 <in.ptau> <out.ptau> [-v]\n' +
-              '       cli.js powersoftau verify <pot.ptau> [-v]\n';
+              '       cli.js powersoftau verify <pot.ptau> [-v]\n' +
+              '       cli.js powersoftau new bn128 <power> <out.ptau> [-v]\n' +
+              '       cli.js powersoftau contribute <in.ptau> <out.ptau> [--name=|-n=name] [-e=entropy] [-v]\n' +
+              '       cli.js powersoftau beacon <in.ptau> <out.ptau> <beaconHashHex> <numIterationsExp> [-n=name] [-v]\n';
 
 async function main(argv) {
   if (argv.length === 5 && argv[0] === 'zkey' && argv[1] === 'export' && argv[2] === 'soliditycalldata') {
@@ -57,6 +65,35 @@ async function main(argv) {
       error: (m) => process.stdout.write(`[ERROR] snarkJS: ${m}\n`),
     };
     return (await powersOfTau.verify(named[2], logger)) ? 0 : 1;
+  }
+  if (argv[0] === 'powersoftau' && ['new', 'contribute', 'beacon'].includes(argv[1])) {
+    const verbose = argv.includes('-v') || argv.includes('--verbose');
+    const logger = verbose ? { info: (m) => process.stdout.write(`[INFO]  snarkJS: ${m}\n`) } : undefined;
+    const pos = argv.filter((a) => !/^(-n|--name|-e|--entropy)=/.test(a) && a !== '-v' && a !== '--verbose');
+    const opt = (re) => {
+      const a = argv.find((x) => re.test(x));
+      return a === undefined ? undefined : a.replace(/^[^=]*=/, '');
+    };
+    const name = opt(/^(-n|--name)=/);
+    if (argv[1] === 'new' && pos.length === 5) {
+      try {
+        await powersOfTau.newAccumulator(pos[2], pos[3], pos[4], logger);
+      } catch (e) {  // an unknown curve or power: snarkjs' error line, exit 1
+        process.stdout.write(`[ERROR] snarkJS: Error: ${e.message}\n`);
+        return 1;
+      }
+      return 0;
+    }
+    if (argv[1] === 'contribute' && pos.length === 4) {
+      await powersOfTau.contribute(pos[2], pos[3], name, opt(/^(-e|--entropy)=/), logger);
+      return 0;
+    }
+    if (argv[1] === 'beacon' && pos.length === 6) {
+      await powersOfTau.beacon(pos[2], pos[3], name, pos[4], pos[5], logger);
+      return 0;
+    }
+    process.stderr.write(USAGE);
+    return 1;
   }
   if (named.length === 5 && argv[0] === 'zkey' && argv[1] === 'verify') {
     // snarkjs' log lines (recalled from snarkjs 0.4.22, unpinned): "[INFO]  snarkJS: ZKey Ok!" and exit 0,

@@ -281,6 +281,59 @@ async function verifyPtau(ptauName, logger, device) {
   return res.valid;
 }
 
+/*
+ * snarkjs' `powersOfTau.newAccumulator(curve, power, fileName, logger)` (the `powersoftau new bn128 <power>`
+ * step, reference circuit/scripts/generate_keys_phase1.sh:6): sections 1-7, every point a generator.  Only
+ * bn128 exists here; any other curve name fails as snarkjs' getCurveFromName does.
+ */
+async function newAccumulator(curve, power, fileName, logger) {
+  const name = String(curve && curve.name ? curve.name : curve);
+  if (!['BN128', 'BN254', 'ALTBN128'].includes(name.toUpperCase().replace(/[^0-9A-Z]/g, ''))) {
+    throw new Error(`Curve not supported: ${name}`);
+  }
+  const p = Number(power);
+  if (!Number.isInteger(p) || p < 1 || p > 28) throw new Error('Invalid power. (Must be between 1 and 28)');
+  const out = addon.ptauNew(p, 0);
+  if (typeof fileName === 'string') fs.writeFileSync(fileName, out);
+  else if (fileName && typeof fileName === 'object' && fileName.type === 'mem') fileName.data = out;
+  if (logger && logger.info) logger.info(`powersoftau new: power ${p}, ${out.length} bytes`);
+  return out;
+}
+
+/*
+ * snarkjs' `powersOfTau.contribute(oldPtauFilename, newPTauFilename, name, entropy, logger)` (the `powersoftau
+ * contribute` step, reference circuit/scripts/generate_keys_phase1.sh:8,10): the key drawn from ChaCha20 seeded
+ * with Blake2b(64 random bytes || entropy), every point of sections 2-5 times its own scalar on the GPU, the
+ * record appended to section 7.  snarkjs asks for the entropy when none is given; here it is then empty and
+ * the 64 random bytes alone seed the draw.
+ */
+async function contributePtau(oldPtauName, newPtauName, name, entropy, logger, device) {
+  const out = addon.ptauContribute(readInput(oldPtauName), entropy == null ? '' : String(entropy),
+                                   name ? String(name) : undefined, device || 0);
+  if (typeof newPtauName === 'string') fs.writeFileSync(newPtauName, out);
+  else if (newPtauName && typeof newPtauName === 'object' && newPtauName.type === 'mem') newPtauName.data = out;
+  if (logger && logger.info) logger.info(`powersoftau contribute ${name || ''}: ${out.length} bytes`);
+  return out;
+}
+
+/*
+ * snarkjs' `powersOfTau.beacon(oldPtauFilename, newPTauFilename, name, beaconHashStr, numIterationsExp, logger)`
+ * (the `powersoftau beacon` step, reference circuit/scripts/generate_keys_phase1.sh:18).
+ */
+async function beaconPtau(oldPtauName, newPtauName, name, beaconHashStr, numIterationsExp, logger, device) {
+  const hex = String(beaconHashStr);
+  const bytes = /^([0-9a-fA-F]{2})+$/.test(hex) ? Buffer.from(hex, 'hex') : Buffer.alloc(0);
+  if (bytes.length === 0) throw new Error('Invalid Beacon Hash. (It must be a valid hexadecimal sequence)');
+  if (bytes.length >= 256) throw new Error('Maximum length of beacon hash is 255 bytes');
+  const e = Number(numIterationsExp);
+  if (!Number.isInteger(e) || e < 10 || e > 63) throw new Error('Invalid numIterationsExp. (Must be between 10 and 63)');
+  const out = addon.ptauBeacon(readInput(oldPtauName), bytes, e, device || 0, name ? String(name) : undefined);
+  if (typeof newPtauName === 'string') fs.writeFileSync(newPtauName, out);
+  else if (newPtauName && typeof newPtauName === 'object' && newPtauName.type === 'mem') newPtauName.data = out;
+  if (logger && logger.info) logger.info(`powersoftau beacon ${name || ''}: ${out.length} bytes`);
+  return out;
+}
+
 function release() {
   for (const h of provers.values()) addon.freeProver(h);
   for (const h of memProvers.values()) addon.freeProver(h);
@@ -292,7 +345,7 @@ module.exports = {
   groth16: { prove, proveBatch },
   proveBatch,
   zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit },
-  powersOfTau: { preparePhase2, verify: verifyPtau },
+  powersOfTau: { newAccumulator, contribute: contributePtau, beacon: beaconPtau, preparePhase2, verify: verifyPtau },
   preparePhase2,
   verifyFromR1cs,
   verifyFromInit,

@@ -38,6 +38,17 @@ export declare const zKey: {
   verifyFromInit(initName: Input, zkeyName: Input, logger?: VerifyLogger, device?: number): Promise<boolean>;
 };
 export declare const powersOfTau: {
+  /** `snarkjs powersoftau new bn128 <power>`: a ceremony file of generators, no contribution; any curve but
+   *  bn128 throws.  Writes fileName when given, returns the file's bytes */
+  newAccumulator(curve: string | { name: string }, power: number, fileName?: string | { type: "mem"; data?: Uint8Array },
+    logger?: Logger): Promise<Uint8Array>;
+  /** `snarkjs powersoftau contribute` on the GPU (zkp_ptau_contribute): the record appended to section 7;
+   *  sections 12-15 of the input are dropped */
+  contribute(oldPtauName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array }, name?: string,
+    entropy?: string, logger?: Logger, device?: number): Promise<Uint8Array>;
+  /** `snarkjs powersoftau beacon` on the GPU (zkp_ptau_beacon); numIterationsExp within 10..63 */
+  beacon(oldPtauName: Input, newPtauName: string | { type: "mem"; data?: Uint8Array } | undefined, name: string | undefined,
+    beaconHashStr: string, numIterationsExp: number, logger?: Logger, device?: number): Promise<Uint8Array>;
   /** `snarkjs powersoftau prepare phase2` on the GPU: the ptau with its Lagrange sections 12-15 (what
    *  `zkey new` reads); writes newPtauName when given, returns the file's bytes */
   preparePhase2(oldPtauName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array }, logger?: Logger,

@@ -15,6 +15,9 @@
  *   zkeyContribute(zkeyBuffer, entropy, name?, device?) -> Buffer (`zkey contribute`)
  *   zkeyVerify(initBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify` against the initial key)
  *   ptauVerify(ptauBuffer, device?)            -> {valid, message} (`snarkjs powersoftau verify`, synchronous)
+ *   ptauNew(power, ceremonyPower?)             -> Buffer (`snarkjs powersoftau new bn128`, host only)
+ *   ptauContribute(ptauBuffer, entropy, name?, device?) -> Buffer (`snarkjs powersoftau contribute`, synchronous)
+ *   ptauBeacon(ptauBuffer, beaconBuffer, numIterationsExp, device?, name?) -> Buffer (`snarkjs powersoftau beacon`)
  *   zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify`)
  *   version()
  * prove()/proveBatch() run on the libuv threadpool (napi_async_work), so the JS main
@@ -286,6 +289,86 @@ static napi_value js_zkey_beacon(napi_env env, napi_callback_info info) {
   const char* nm = argc > 4 ? opt_string(env, argv[4], name, sizeof name) : NULL;
   zkp_status st = zkp_zkey_beacon_named(device, (const uint8_t*)zkey, zkey_len, (const uint8_t*)beacon, beacon_len, e,
                                         nm, &out, &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return buffer_out(env, out, out_len);
+}
+
+/* ptauNew(power, ceremonyPower?) -> Buffer: `snarkjs powersoftau new bn128 <power>` (zkp_ptau_new), host only */
+static napi_value js_ptau_new(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  uint32_t power = 0, ceremony = 0;
+  if (argc < 1 || napi_get_value_uint32(env, argv[0], &power) != napi_ok) {
+    napi_throw_type_error(env, NULL, "ptauNew(power, ceremonyPower?)");
+    return NULL;
+  }
+  if (argc > 1) napi_get_value_uint32(env, argv[1], &ceremony);
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  zkp_status st = zkp_ptau_new(power, ceremony, &out, &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return buffer_out(env, out, out_len);
+}
+
+/* ptauContribute(ptauBuffer, entropyString, nameString?, device?) -> Buffer: `snarkjs powersoftau contribute`
+ * (zkp_ptau_contribute, 64 bytes of the OS CSPRNG mixed with the entropy), synchronous -- a setup step */
+static napi_value js_ptau_contribute(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false;
+  char ent[4096], name[256];
+  const char* e = NULL;
+  if (argc >= 2) {
+    napi_is_buffer(env, argv[0], &b0);
+    e = opt_string(env, argv[1], ent, sizeof ent);
+  }
+  if (!b0 || !e) {
+    napi_throw_type_error(env, NULL, "ptauContribute(ptauBuffer, entropyString, nameString?, device?)");
+    return NULL;
+  }
+  const char* nm = argc > 2 ? opt_string(env, argv[2], name, sizeof name) : NULL;
+  int device = 0;
+  if (argc > 3) napi_get_value_int32(env, argv[3], &device);
+  void* ptau;
+  size_t ptau_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &ptau, &ptau_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  zkp_status st = zkp_ptau_contribute(device, (const uint8_t*)ptau, ptau_len, NULL, e, nm, &out, &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return buffer_out(env, out, out_len);
+}
+
+/* ptauBeacon(ptauBuffer, beaconBuffer, numIterationsExp, device?, nameString?) -> Buffer: `snarkjs powersoftau
+ * beacon` (zkp_ptau_beacon), synchronous -- a setup step */
+static napi_value js_ptau_beacon(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false, b1 = false;
+  uint32_t e = 0;
+  if (argc >= 3) {
+    napi_is_buffer(env, argv[0], &b0);
+    napi_is_buffer(env, argv[1], &b1);
+  }
+  if (!b0 || !b1 || napi_get_value_uint32(env, argv[2], &e) != napi_ok) {
+    napi_throw_type_error(env, NULL, "ptauBeacon(ptauBuffer, beaconBuffer, numIterationsExp, device?, nameString?)");
+    return NULL;
+  }
+  int device = 0;
+  if (argc > 3) napi_get_value_int32(env, argv[3], &device);
+  void *ptau, *beacon;
+  size_t ptau_len, beacon_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &ptau, &ptau_len));
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &beacon, &beacon_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  char name[256];
+  const char* nm = argc > 4 ? opt_string(env, argv[4], name, sizeof name) : NULL;
+  zkp_status st = zkp_ptau_beacon(device, (const uint8_t*)ptau, ptau_len, (const uint8_t*)beacon, beacon_len, e, nm,
+                                  &out, &out_len);
   if (st != ZKP_OK) return throw_status(env, st);
   return buffer_out(env, out, out_len);
 }
@@ -685,6 +768,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"zkeyContribute", NULL, js_zkey_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerify", NULL, js_zkey_verify, NULL, NULL, NULL, napi_default, NULL},
       {"ptauVerify", NULL, js_ptau_verify, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauNew", NULL, js_ptau_new, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauContribute", NULL, js_ptau_contribute, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauBeacon", NULL, js_ptau_beacon, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromR1cs", NULL, js_zkey_verify_r1cs, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);

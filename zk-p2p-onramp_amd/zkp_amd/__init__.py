@@ -169,6 +169,17 @@ def load_library(path: str = LIB_PATH):
             lib.zkp_ptau_verify_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
             lib.zkp_g2_subgroup_check.argtypes = [ctypes.c_int, u8p, sz, u64p, u64p]
             lib.zkp_rlc_pairs.argtypes = [ctypes.c_int, ctypes.c_int, u8p, ctypes.c_uint64, u8p, sz, u8p, ip, u8p, ip]
+        if hasattr(lib, "zkp_ptau_contribute"):  # powersoftau new / contribute / beacon
+            lib.zkp_ptau_new.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+            lib.zkp_ptau_contribute.argtypes = [ctypes.c_int, u8p, sz, u8p, ctypes.c_char_p, ctypes.c_char_p,
+                                                ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+            lib.zkp_ptau_beacon.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, ctypes.c_uint32, ctypes.c_char_p,
+                                            ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+            lib.zkp_ptau_contribute_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+            lib.zkp_points_scale_powers.argtypes = [ctypes.c_int, ctypes.c_int, u8p, sz, u8p, u8p, u8p]
+            for name in ("zkp_ptau_new", "zkp_ptau_contribute", "zkp_ptau_beacon", "zkp_ptau_contribute_timings",
+                         "zkp_points_scale_powers"):
+                getattr(lib, name).restype = ctypes.c_int
         for name in ("zkp_zkey_verify_frominit", "zkp_zkey_verify", "zkp_zkey_verify_timings", "zkp_rlc_coeffs",
                      "zkp_points_check", "zkp_rlc_g1", "zkp_ptau_verify", "zkp_ptau_verify_sections", "zkp_ptau_verify_timings",
                      "zkp_g2_subgroup_check", "zkp_rlc_pairs"):
@@ -816,6 +827,76 @@ def ptau_verify_timings() -> dict:
             "accumulate_pairs", "accumulate_lagrange", "accumulate_tau", "host_fold", "host_pairings", "chunks",
             "contributions", "first_challenge", "next_challenge"]
     return dict(zip(keys, list(out)))
+
+
+def _take(lib, out, n) -> bytes:
+    try:
+        return _copy_out(out, n.value)
+    finally:
+        lib.zkp_buffer_free(out)
+
+
+def ptau_new(power: int, ceremony_power: int = 0) -> bytes:
+    """`snarkjs powersoftau new bn128 <power>` (zkp_ptau_new; host only): sections 1-7, every point a
+    generator, no contribution.  ceremony_power 0: = power."""
+    lib = load_library()
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_ptau_new(power, ceremony_power, ctypes.byref(out), ctypes.byref(n)))
+    return _take(lib, out, n)
+
+
+def ptau_contribute(ptau: bytes, entropy: str, rand64: bytes = None, name=None, device: int = 0) -> bytes:
+    """`snarkjs powersoftau contribute <in> <out> -e=<entropy> [--name=]` (zkp_ptau_contribute): every point of
+    sections 2-5 times its own scalar on the GPU, the record appended to section 7.  rand64 = the 64 random
+    bytes mixed with the entropy (None: the OS CSPRNG; tests pass fixed bytes).  Sections 12-15 are dropped."""
+    lib = load_library()
+    pp, plen, pk = _in(ptau)
+    rp = None
+    if rand64 is not None:
+        if len(rand64) != 64:
+            raise ValueError("rand64 must be 64 bytes")
+        rp, rk = _buf(bytes(rand64))
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_ptau_contribute(device, pp, plen, rp, entropy.encode(), None if name is None else name.encode(),
+                                   ctypes.byref(out), ctypes.byref(n)))
+    return _take(lib, out, n)
+
+
+def ptau_beacon(ptau: bytes, beacon: bytes, num_iterations_exp: int, name=None, device: int = 0) -> bytes:
+    """`snarkjs powersoftau beacon <in> <out> <beaconHashHex> <numIterationsExp> [-n=]` (zkp_ptau_beacon)."""
+    lib = load_library()
+    pp, plen, pk = _in(ptau)
+    bp, bk = _buf(bytes(beacon) or b"\0")
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_ptau_beacon(device, pp, plen, bp, len(beacon), num_iterations_exp,
+                               None if name is None else name.encode(), ctypes.byref(out), ctypes.byref(n)))
+    return _take(lib, out, n)
+
+
+def ptau_contribute_timings() -> dict:
+    """ms of the calling thread's last ptau_contribute / ptau_beacon (zkp_ptau_contribute_timings)."""
+    out = (ctypes.c_double * 12)()
+    _check(load_library().zkp_ptau_contribute_timings(out, 12))
+    keys = ["total", "parse_point_check", "challenge", "key_draw", "upload", "g1_scale", "g2_scale", "encode", "download",
+            "partial_hash", "next_challenge", "chunks"]
+    return dict(zip(keys, list(out)))
+
+
+def points_scale_powers(points_lem: bytes, first: int, ratio: int, g2: bool = False, device: int = 0) -> bytes:
+    """Kernel-level (zkp_points_scale_powers): out_i = (first * ratio^i) * P_i over zkey-layout points."""
+    pb = 128 if g2 else 64
+    if len(points_lem) % pb:
+        raise ValueError("points_scale_powers: points of %d bytes each" % pb)
+    pp, pk = _buf(bytes(points_lem) or b"\0")
+    fp, fk = _buf(int(first).to_bytes(32, "little"))
+    rp, rk = _buf(int(ratio).to_bytes(32, "little"))
+    out = (ctypes.c_uint8 * max(1, len(points_lem)))()
+    _check(load_library().zkp_points_scale_powers(device, 1 if g2 else 0, pp, len(points_lem) // pb, fp, rp,
+                                                  ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8))))
+    return bytes(out)[:len(points_lem)]
 
 
 def g2_subgroup_check(points_lem: bytes, device: int = 0):
