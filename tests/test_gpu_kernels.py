@@ -86,6 +86,8 @@ def test_msm_g1_skewed_and_multigroup(monkeypatch, dense):
         (pts, [1] * 150 + uni[:150], 0, 0),          # circuit-like: half the entries in bucket 0
         (pts, [1] * 300, 8, 0),
         (pts, uni, 8, 4),                             # 8 bucket groups
+        (pts, uni, 21, 1),                            # 13 groups of 2^20 buckets: a 24-bit bucket key, so 6 bucket
+                                                      # bits per sub-bin and the tiled pass C on the dense plan too
         (pts, [0] * 299 + [5], 0, 0),
         (pts[:1], [0], 0, 0),
     ]

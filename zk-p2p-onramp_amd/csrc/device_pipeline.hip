@@ -180,14 +180,8 @@ static void choose_msm_params(size_t n_w, size_t n_h, const MsmOptions& o, MsmPa
   // digits of a 0/1-heavy witness are single entries) prefer one bit less than lg n - 4, the
   // uniform-scalar H MSM one bit more (fewer windows; the bucket reduction is cheap), moved off the
   // widths whose top window collapses into a few buckets (dense_window_bits)
-  auto lg = [](size_t n) {
-    int l = 0;
-    while ((size_t(1) << l) < n) ++l;
-    return l;
-  };
-  auto clampc = [](int c) { return c < 8 ? 8 : (c > 20 ? 20 : c); };
-  const int cw = o.w ? o.w : clampc(lg(n_w) - 5);
-  const int ch = o.h ? o.h : dense_window_bits(clampc(lg(n_h) - 3), n_h);
+  const int cw = o.w ? o.w : std::min(20, std::max(8, lg_ceil(n_w) - 5));
+  const int ch = o.h ? o.h : h_window_bits(n_h);
   auto tune = [&] { apply_task_options(pw, o.task_w, o), apply_task_options(ph, o.task_h, o); };
   pw = make_params(n_w, cw, o.depth);
   ph = make_params(n_h, ch, o.depth);
@@ -399,6 +393,7 @@ void DevicePipeline::build_engines(WSet& w) {
   // plan's own outputs by its mask's count
   // (a shared build sorts the union of the plans' signals: nearly the fullest plan's, C's, at the Venmo key)
   const bool shared = sp && share_ && w.memb;
+  w.shared_build = shared;
   const size_t most = std::max(w.present[PL_B], std::max(w.present[PL_A], w.present[PL_C]));
   auto scratch = std::make_shared<MsmSortScratch>(
       nv_, shared ? (w.memb->any.bits ? w.memb->any.count : nv_) : most, w.pw, shared ? (int)NPLAN : 1);
@@ -528,8 +523,7 @@ DevicePipeline::MsmOut DevicePipeline::prove_uploaded(int k, float h2d_ms, const
   std::lock_guard<std::mutex> lk(mu_);
   HIPX(hipSetDevice(dev_));
   maybe_inject_fault();
-  HIPX(hipEventRecord(ev_[EV_H2D_BEGIN], s0_));
-  HIPX(hipEventRecord(ev_[EV_H2D_END], s0_));
+  record_no_transfer();
   MsmOut o = prove_dev(up_[k], early, pick_wset(up_large_[k]));
   o.ms[0] = h2d_ms;
   return o;
@@ -631,8 +625,7 @@ DevicePipeline::MsmOut DevicePipeline::prove_ext_staged(int slot, const void* co
   const uint32_t* d = slot_ptr(slot);
   for (int v = 0; v < 3; ++v)
     if (!abc[v]) throw ZkpError(ZKP_ERR_INVALID_ARG, "partial prove: null quotient slice");
-  HIPX(hipEventRecord(ev_[EV_H2D_BEGIN], s0_));
-  HIPX(hipEventRecord(ev_[EV_H2D_END], s0_));
+  record_no_transfer();
   for (int v = 0; v < 3; ++v) ext_abc_[v] = static_cast<const uint32_t*>(abc[v]);
   struct ClearExt {  // ext_abc_ is set for this proof only, however it ends
     const uint32_t** p;
@@ -658,149 +651,156 @@ DevicePipeline::MsmOut DevicePipeline::prove_staged(int slot, const EarlyFn& ear
 DevicePipeline::MsmOut DevicePipeline::prove_resident(const uint32_t* d_wit, const EarlyFn& early, double large_frac) {
   std::lock_guard<std::mutex> lk(mu_);
   HIPX(hipSetDevice(dev_));
-  HIPX(hipEventRecord(ev_[EV_H2D_BEGIN], s0_));
-  HIPX(hipEventRecord(ev_[EV_H2D_END], s0_));
+  record_no_transfer();
   return prove_dev(d_wit, early, pick_wset(large_frac));
 }
 
+void DevicePipeline::record_no_transfer() {
+  HIPX(hipEventRecord(ev_[EV_H2D_BEGIN], s0_));
+  HIPX(hipEventRecord(ev_[EV_H2D_END], s0_));
+}
+
+struct DevicePipeline::ProofRun {
+  WSet& ws;  // the witness configuration the proof takes
+  int wset;
+  const uint32_t* d_wit;
+  uint32_t *wa, *wh, *wb2;  // the group sums' slots in dwin_: A | B1 | C, H, B2
+  int g2first;              // g2first_, off under ZKP_SERIAL
+  bool cgate;               // cgate_, off under ZKP_SERIAL
+  // opened by enqueue_g1 once plan B is enqueued, by enqueue_g2 once EV_G2_ACC is recorded (g2first)
+  // and by enqueue_h once EV_QUOT is recorded (cgate)
+  Gate planned, g2acc, quot;
+  std::exception_ptr err[3];  // of enqueue_g1, enqueue_g2, enqueue_h
+};
+
+// s3: the witness plans B, A, C (one per mask of finite bases, each MSM takes its table's).  With
+// ZKP_MSM share=1 (default) ONE build fills the three plans (MsmPlan::build_shared), so all are ready
+// before the quotient ends; share=0 builds B, A, C back to back.
+// s2: the G1 accumulations A, B1, C back to back; s3 finishes each (merges + reduction: latency-bound
+// chains) while s2 accumulates the next.  A starts when the G2 accumulation ends: the G2 finish (a
+// latency-bound chain on the low-priority s1) then runs beside A, B1 and C instead of waiting out the
+// H accumulation and sharing the proof's tail with the H finish (+0.4 %, 7 of 8 alternated pairs:
+// profiles/g2_first_ab_r06.txt).  cgate=1 holds C's accumulation until the quotient is done (EV_QUOT).
+void DevicePipeline::enqueue_g1(ProofRun& r) {
+  WSet& ws = r.ws;
+  try {
+    HIPX(hipSetDevice(dev_));
+    HIPX(hipStreamWaitEvent(s2_, ev_[EV_H2D_END], 0));
+    HIPX(hipEventRecord(ev_[EV_G1_BEGIN], s2_));
+    HIPX(hipStreamWaitEvent(ws.plan[PL_B]->stream(), ev_[EV_H2D_END], 0));
+    if (ws.shared_build) {  // one build fills every plan
+      MsmPlan* own[NPLAN];
+      for (int p = 0; p < NPLAN; ++p) own[p] = ws.own[p].get();
+      MsmPlan::build_shared(own, r.d_wit + wlo_ * 8, whi_ - wlo_, *ws.memb);
+      r.planned.open();
+    } else {
+      for (int p = 0; p < NPLAN; ++p) {
+        if (ws.own[p]) ws.own[p]->build(r.d_wit + wlo_ * 8, whi_ - wlo_, ws.mask[p], ws.present[p]);
+        if (p == PL_B) r.planned.open();
+      }
+    }
+    const MsmBases* tabs[3] = {ws.ta.get(), ws.tb1.get(), ws.tc.get()};
+    const MsmPlan* plans[3] = {ws.plan[PL_A], ws.plan[PL_B], ws.plan[PL_C]};
+    for (int m = 0; m < 3; ++m) {
+      if (r.g2first && m == r.g2first - 1) {
+        r.g2acc.wait();
+        HIPX(hipStreamWaitEvent(s2_, ev_[EV_G2_ACC], 0));
+      }
+      if (r.cgate && m == 2) {  // C fills the window of the H plan's sort
+        r.quot.wait();
+        HIPX(hipStreamWaitEvent(s2_, ev_[EV_QUOT], 0));
+      }
+      ws.g1[m]->accumulate(*plans[m], *tabs[m]);
+      HIPX(hipEventRecord(ev_[EV_ACC_A + m], s2_));
+      HIPX(hipStreamWaitEvent(s3_, ev_[EV_ACC_A + m], 0));
+      ws.g1[m]->finish(*plans[m], r.wa + m * wina_, s3_);
+      if (serial_) {  // profiling: no overlap between the finish and the next accumulation
+        HIPX(hipEventRecord(ev_[EV_FINISH], s3_));
+        HIPX(hipStreamWaitEvent(s2_, ev_[EV_FINISH], 0));
+      }
+    }
+    HIPX(hipEventRecord(ev_[EV_G1_END], s3_));
+  } catch (...) {
+    r.err[0] = std::current_exception();
+    r.planned.fail(r.err[0]);
+  }
+}
+
+// s1: the G2 MSM B2 on plan B, once that plan is enqueued (s1 then waits on its ready()): the G2
+// accumulation comes first in the proof
+void DevicePipeline::enqueue_g2(ProofRun& r) {
+  WSet& ws = r.ws;
+  try {
+    r.planned.wait();
+    HIPX(hipSetDevice(dev_));
+    if (serial_) HIPX(hipStreamWaitEvent(s1_, ev_[EV_G1_END], 0));
+    HIPX(hipEventRecord(ev_[EV_G2_BEGIN], s1_));
+    // the finish on s1 too: s3 is in-order, the G1 finishes must not queue behind it (gating the
+    // G2 finish on the H plan, on either stream, measured +0.9 ms: profiles/g2_finish_r03.txt)
+    ws.g2->accumulate(*ws.plan[PL_B], *ws.tb2);
+    if (r.g2first) {
+      HIPX(hipEventRecord(ev_[EV_G2_ACC], s1_));
+      r.g2acc.open();
+    }
+    ws.g2->finish(*ws.plan[PL_B], r.wb2, s1_);
+    HIPX(hipEventRecord(ev_[EV_G2_END], s1_));
+  } catch (...) {
+    r.err[1] = std::current_exception();
+    r.g2acc.fail(r.err[1]);
+  }
+}
+
+// s0: quotient (buildABC, 3 coset NTTs, joinABC), H plan, H MSM
+void DevicePipeline::enqueue_h(ProofRun& r) {
+  try {
+    if (serial_) HIPX(hipStreamWaitEvent(s0_, ev_[EV_G2_END], 0));
+    if (ext_abc_[0]) {  // distributed quotient: only the join of this domain slice
+      HIPX(hipEventRecord(ev_[EV_ABC], s0_));
+      launch_join_abc(ext_abc_[0], ext_abc_[1], ext_abc_[2], (uint32_t)(hhi_ - hlo_), pscal_ + hlo_ * 8, s0_);
+      HIPX(hipEventRecord(ev_[EV_QUOT], s0_));
+    } else {
+      enqueue_quotient(r.d_wit);
+    }
+    r.quot.open();
+    plan_h_->build(pscal_ + hlo_ * 8, hhi_ - hlo_);
+    g1h_->run(*plan_h_, *th_, r.wh);
+  } catch (...) {
+    r.err[2] = std::current_exception();
+    r.quot.fail(r.err[2]);
+  }
+}
+
 DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const EarlyFn& early, int wsel) {
-  WSet& ws = ws_[wsel < nws_ ? wsel : 0];
-  const size_t win2 = ws.g2->window_words();
+  const int wset = wsel < nws_ ? wsel : 0;
   // group-sum layout in dwin_ (slots sized for the larger witness configuration): A | B1 | C
   // (engines ws.g1) | H (g1h) | B2 (ws.g2)
-  uint32_t* wa = dwin_;
   uint32_t* wh = dwin_ + 3 * wina_;
-  uint32_t* wb2 = wh + winh_;
-  // s3: the witness plans B, A, C (one per mask of finite bases, each MSM takes its table's);
-  // s2: the G1 accumulations A, B1, C back to back; s3 finishes each
-  // (merges + reduction: latency-bound chains) while s2 accumulates the next;
-  // s1: G2 MSM B2 on the same plan; s0: quotient (buildABC, 3 coset NTTs, joinABC),
-  // H plan, H MSM.  A starts when the G2 accumulation ends: the G2 finish (a latency-bound chain
-  // on the low-priority s1) then runs beside A, B1 and C instead of waiting out the H accumulation
-  // and sharing the proof's tail with the H finish (+0.4 %, 7 of 8 alternated pairs:
-  // profiles/g2_first_ab_r06.txt).
+  ProofRun r{ws_[wset], wset, d_wit, dwin_, wh, wh + winh_, serial_ ? 0 : g2first_, !serial_ && cgate_};
   // Nothing here blocks on the device (a plan's exact digit count stays there), but a proof enqueues
-  // a few hundred launches, so each stream is fed from its own host thread; the G2 thread starts once
-  // plan B is enqueued (its stream then waits on that plan's ready()): the G2 accumulation comes first
-  // in the proof.  With ZKP_MSM share=1 (default) ONE build fills the three plans
-  // (MsmPlan::build_shared), so all are ready before the quotient ends; share=0 builds B, A, C back
-  // to back.  cgate=1 holds C's accumulation until the quotient is done (EV_QUOT).
-  // ZKP_SERIAL=1 (profiling only) chains the three streams so every kernel runs alone.
-  std::exception_ptr err[3];
-  std::promise<void> planned;
-  std::shared_future<void> planned_f = planned.get_future().share();
-  bool planned_set = false;
-  const int g2first = serial_ ? 0 : g2first_;
-  std::promise<void> g2acc;
-  std::shared_future<void> g2acc_f = g2acc.get_future().share();
-  bool g2acc_set = false;
-  const bool cgate = !serial_ && cgate_;
-  std::promise<void> quot;  // EV_QUOT recorded for this proof (cgate)
-  std::shared_future<void> quot_f = quot.get_future().share();
-  bool quot_set = false;
-  auto g1_job = [&] {
-    try {
-      HIPX(hipSetDevice(dev_));
-      HIPX(hipStreamWaitEvent(s2_, ev_[EV_H2D_END], 0));
-      HIPX(hipEventRecord(ev_[EV_G1_BEGIN], s2_));
-      HIPX(hipStreamWaitEvent(ws.plan[PL_B]->stream(), ev_[EV_H2D_END], 0));
-      if (sparse_ && share_ && ws.memb) {  // one build fills every plan
-        MsmPlan* own[NPLAN];
-        for (int p = 0; p < NPLAN; ++p) own[p] = ws.own[p].get();
-        MsmPlan::build_shared(own, d_wit + wlo_ * 8, whi_ - wlo_, *ws.memb);
-        planned.set_value();
-        planned_set = true;
-      } else {
-        for (int p = 0; p < NPLAN; ++p) {
-          if (ws.own[p]) ws.own[p]->build(d_wit + wlo_ * 8, whi_ - wlo_, ws.mask[p], ws.present[p]);
-          if (p == PL_B) {
-            planned.set_value();
-            planned_set = true;
-          }
-        }
-      }
-      const MsmBases* tabs[3] = {ws.ta.get(), ws.tb1.get(), ws.tc.get()};
-      const MsmPlan* plans[3] = {ws.plan[PL_A], ws.plan[PL_B], ws.plan[PL_C]};
-      for (int m = 0; m < 3; ++m) {
-        if (g2first && m == g2first - 1) {
-          g2acc_f.get();
-          HIPX(hipStreamWaitEvent(s2_, ev_[EV_G2_ACC], 0));
-        }
-        if (cgate && m == 2) {  // C fills the window of the H plan's sort
-          quot_f.get();
-          HIPX(hipStreamWaitEvent(s2_, ev_[EV_QUOT], 0));
-        }
-        ws.g1[m]->accumulate(*plans[m], *tabs[m]);
-        HIPX(hipEventRecord(ev_[EV_ACC_A + m], s2_));
-        HIPX(hipStreamWaitEvent(s3_, ev_[EV_ACC_A + m], 0));
-        ws.g1[m]->finish(*plans[m], wa + m * wina_, s3_);
-        if (serial_) {  // profiling: no overlap between the finish and the next accumulation
-          HIPX(hipEventRecord(ev_[EV_FINISH], s3_));
-          HIPX(hipStreamWaitEvent(s2_, ev_[EV_FINISH], 0));
-        }
-      }
-      HIPX(hipEventRecord(ev_[EV_G1_END], s3_));
-    } catch (...) {
-      err[0] = std::current_exception();
-      if (!planned_set) planned.set_exception(std::current_exception());
-    }
-  };
-  auto g2_job = [&] {
-    try {
-      planned_f.get();
-      HIPX(hipSetDevice(dev_));
-      if (serial_) HIPX(hipStreamWaitEvent(s1_, ev_[EV_G1_END], 0));
-      HIPX(hipEventRecord(ev_[EV_G2_BEGIN], s1_));
-      // the finish on s1 too: s3 is in-order, the G1 finishes must not queue behind it (gating the
-      // G2 finish on the H plan, on either stream, measured +0.9 ms: profiles/g2_finish_r03.txt)
-      ws.g2->accumulate(*ws.plan[PL_B], *ws.tb2);
-      if (g2first) {
-        HIPX(hipEventRecord(ev_[EV_G2_ACC], s1_));
-        g2acc.set_value();
-        g2acc_set = true;
-      }
-      ws.g2->finish(*ws.plan[PL_B], wb2, s1_);
-      HIPX(hipEventRecord(ev_[EV_G2_END], s1_));
-    } catch (...) {
-      err[1] = std::current_exception();
-      if (g2first && !g2acc_set) g2acc.set_exception(std::current_exception());
-    }
-  };
-  auto h_job = [&] {
-    try {
-      if (serial_) HIPX(hipStreamWaitEvent(s0_, ev_[EV_G2_END], 0));
-      if (ext_abc_[0]) {  // distributed quotient: only the join of this domain slice
-        HIPX(hipEventRecord(ev_[EV_ABC], s0_));
-        launch_join_abc(ext_abc_[0], ext_abc_[1], ext_abc_[2], (uint32_t)(hhi_ - hlo_), pscal_ + hlo_ * 8, s0_);
-        HIPX(hipEventRecord(ev_[EV_QUOT], s0_));
-      } else {
-        enqueue_quotient(d_wit);
-      }
-      quot.set_value();
-      quot_set = true;
-      plan_h_->build(pscal_ + hlo_ * 8, hhi_ - hlo_);
-      g1h_->run(*plan_h_, *th_, wh);
-    } catch (...) {
-      err[2] = std::current_exception();
-      if (!quot_set) quot.set_exception(std::current_exception());
-    }
-  };
+  // a few hundred launches, so each stream is fed from its own host thread; the G2 thread starts first
+  // and waits for plan B to be enqueued.  ZKP_SERIAL=1 (profiling only) chains the three streams so
+  // every kernel runs alone.
   if (serial_) {
-    g1_job();
-    if (!err[0]) g2_job();
-    if (!err[0] && !err[1]) h_job();
+    enqueue_g1(r);
+    if (!r.err[0]) enqueue_g2(r);
+    if (!r.err[0] && !r.err[1]) enqueue_h(r);
   } else {
-    jt_g2_.start(g2_job);
-    jt_g1_.start(g1_job);
-    h_job();
+    jt_g2_.start([&] { enqueue_g2(r); });
+    jt_g1_.start([&] { enqueue_g1(r); });
+    enqueue_h(r);
     jt_g1_.wait();
     jt_g2_.wait();
   }
-  for (auto& e : err)
+  for (auto& e : r.err)
     if (e) {
       (void)hipDeviceSynchronize();  // let every enqueued kernel drain before buffers are reused
       std::rethrow_exception(e);
     }
+  return collect_proof(r, early);
+}
+
+DevicePipeline::MsmOut DevicePipeline::collect_proof(const ProofRun& r, const EarlyFn& early) {
+  WSet& ws = r.ws;
   HIPX(hipEventRecord(ev_[EV_H_END], s0_));
   // the witness MSMs' group sums (A | B1 | C, B2) go to the host as soon as their finishes end
   // (s3 holds the G1 finishes; it waits for the G2 finish), so the host folds them and the caller
@@ -808,9 +808,9 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
   // affine conversions and the H fold remain after the device is done
   HIPX(hipStreamWaitEvent(s3_, ev_[EV_G2_END], 0));
   HIPX(hipMemcpyAsync(hwin_, dwin_, 3 * wina_ * 4, hipMemcpyDeviceToHost, s3_));
-  HIPX(hipMemcpyAsync(hwin_ + 3 * wina_ + winh_, wb2, win2 * 4, hipMemcpyDeviceToHost, s3_));
+  HIPX(hipMemcpyAsync(hwin_ + 3 * wina_ + winh_, r.wb2, ws.g2->window_words() * 4, hipMemcpyDeviceToHost, s3_));
   HIPX(hipEventRecord(ev_[EV_WIT_COPIED], s3_));
-  HIPX(hipMemcpyAsync(hwin_ + 3 * wina_, wh, winh_ * 4, hipMemcpyDeviceToHost, s0_));
+  HIPX(hipMemcpyAsync(hwin_ + 3 * wina_, r.wh, winh_ * 4, hipMemcpyDeviceToHost, s0_));
   HIPX(hipEventRecord(ev_[EV_H_COPIED], s0_));
   MsmOut o;
   const MsmParams& pa = ws.g1[0]->params();
@@ -834,7 +834,7 @@ DevicePipeline::MsmOut DevicePipeline::prove_dev(const uint32_t* d_wit, const Ea
   for (int m = 0; m < 3; ++m) collect_kind(*ws.g1[m], m, stats_g1_);
   collect_kind(*g1h_, 3, stats_g1_);
   collect_kind(*ws.g2, 4, stats_g2_);
-  o.wset = wsel < nws_ ? wsel : 0;
+  o.wset = r.wset;
   o.h = msm_fold<HFq>(hwin_ + 3 * wina_, ph);
   HIPX(hipEventElapsedTime(&o.ms[0], ev_[EV_H2D_BEGIN], ev_[EV_H2D_END]));  // wtns H2D
   HIPX(hipEventElapsedTime(&o.ms[1], ev_[EV_H2D_END], ev_[EV_ABC]));  // buildABC

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <future>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -138,6 +139,23 @@ class JobThread {
   std::function<void()> job_;
   bool stop_ = false, done_ = true;
   std::thread th_;  // last: started once the state above exists
+};
+
+// A one-shot hand-off between two of a proof's host threads: the consumer's wait() blocks until the
+// producer opens the gate, or rethrows what the producer failed it with.  fail() after open() does
+// nothing: a producer that throws once the consumer may run keeps the error to itself.
+class Gate {
+ public:
+  void open() { p_.set_value(), opened_ = true; }
+  void fail(const std::exception_ptr& e) {
+    if (!opened_) p_.set_exception(e);
+  }
+  void wait() { f_.get(); }
+
+ private:
+  std::promise<void> p_;
+  std::shared_future<void> f_ = p_.get_future().share();
+  bool opened_ = false;
 };
 
 // ------------------------------------------------------------------ device pipeline
@@ -283,7 +301,8 @@ class DevicePipeline {
   // claimed by a staged caller (Prover::prove_staged spreads concurrent callers over the pipelines)
   std::atomic<bool> staged_busy{false};
 
-  // the whole device pipeline on a resident witness (caller holds mu_, EV_H2D_BEGIN / _END recorded)
+  // the whole device pipeline on a resident witness (caller holds mu_, EV_H2D_BEGIN / _END recorded):
+  // starts the three enqueue jobs (enqueue_g1, enqueue_g2, enqueue_h), then collect_proof
   MsmOut prove_dev(const uint32_t* d_wit, const EarlyFn& early = {}, int wsel = 0);
 
  private:
@@ -337,6 +356,7 @@ class DevicePipeline {
     MsmPlan* plan[NPLAN] = {};            // the plan each slot takes
     const uint32_t* mask[NPLAN] = {};  // each slot's index list of finite bases (null: no mask)
     size_t present[NPLAN] = {};
+    bool shared_build = false;  // one MsmPlan::build_shared fills the plans (sparse, share=1 and a membership table)
     std::unique_ptr<MsmEngine> g1[3], g2;  // g1: A, B1, C
     void drop_engines() {
       for (int p = 0; p < NPLAN; ++p) own[p].reset(), plan[p] = nullptr;
@@ -351,6 +371,18 @@ class DevicePipeline {
   bool wset2_tables_ = false;  // this device holds the second configuration's tables (add_second_wset)
   size_t nv_ = 0;              // witness signals of this pipeline's slice
   void build_engines(WSet& w);
+  // one proof's enqueue state (device_pipeline.hip) and its three jobs, one per host thread and stream
+  // family: the witness plans and the G1 MSMs A, B1, C (s3, s2), the G2 MSM B2 (s1), the quotient and
+  // the H MSM (s0).  Each records its own failure in the proof's err[] slot.
+  struct ProofRun;
+  void enqueue_g1(ProofRun& r);
+  void enqueue_g2(ProofRun& r);
+  void enqueue_h(ProofRun& r);
+  // what follows the jobs: the group sums to the host, the folds (`early` once A, B1, C, B2 are
+  // folded), the engines' statistics and the stage times
+  MsmOut collect_proof(const ProofRun& r, const EarlyFn& early);
+  // EV_H2D_BEGIN / _END of a proof without a witness transfer
+  void record_no_transfer();
   std::shared_ptr<MsmBases> th_;  // shared by the pipelines of one device
   DevBuf<> rowptr_[2], col_[2], val_[2];
   static constexpr int NUP = 2;    // witness upload slots (double buffering)

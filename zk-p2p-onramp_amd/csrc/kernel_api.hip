@@ -43,10 +43,8 @@ struct MsmRig {
     // [8, 20] and moved off a collapsed top window); measured on configs[1] (G1 2^20, uniform
     // scalars, 273c6e8:tools/gpu/experiments/r2_msm_c.sh): 1.84 ms against 2.06 ms for a compacted plan at
     // c = lg n - 4.  ZKP_MSM plan=compact selects the witness plan's variant (tests).
-    int lg = 0;
-    while ((size_t(1) << lg) < n) ++lg;
     const MsmOptions opt = msm_options();
-    const int c_auto = opt.h ? opt.h : dense_window_bits(std::min(20, std::max(8, lg - 3)), n);
+    const int c_auto = opt.h ? opt.h : h_window_bits(n);
     prm = make_params(std::max<size_t>(n, 1), c ? c : c_auto, depth);
     apply_task_options(prm, opt.task_h, opt);  // the H plan's task size too (choose_msm_params)
     bases = std::make_unique<MsmBases>(curve, n, prm.c, prm.depth);
@@ -150,11 +148,9 @@ float bench_ntt(int device, int log_n, int count, int warmup, int iters) {
 
 void ntt_fr(int device, uint8_t* data, size_t n, int mode) {
   if (n == 0 || (n & (n - 1))) throw ZkpError(ZKP_ERR_INVALID_ARG, "NTT size must be a power of two");
-  int k = 0;
-  while ((size_t(1) << k) < n) ++k;
   HIPX(hipSetDevice(device));
   Stream st(hipStreamNonBlocking);
-  NttEngine eng(k, st);
+  NttEngine eng(lg_ceil(n), st);
   DevBuf<> d(n * 8);
   HIPX(hipMemcpyAsync(d, data, n * 32, hipMemcpyHostToDevice, st));
   launch_fr_to_dev(d, n, st);

@@ -399,9 +399,9 @@ MsmSortScratch::MsmSortScratch(size_t max_n_, size_t max_present, const MsmParam
     throw std::invalid_argument("MSM: window bits outside the plan's range");
   if (max_n * prm.depth >= (size_t(1) << 31)) throw std::runtime_error("MSM size too large for 31-bit base indices");
   nbuckets = prm.buckets();
-  max_entries = std::max<size_t>(std::min(max_present, max_n), 1) * prm.windows;
+  max_entries = prm.max_entries(max_n, max_present);
   if (max_entries >= 0xffffffffull) throw std::runtime_error("MSM size too large for 32-bit entry indices");
-  max_tasks = (max_entries + prm.S - 1) / prm.S + nbuckets;
+  max_tasks = prm.max_tasks(max_entries);
   merge_levels = msm_merge_levels(max_n, prm);
   cnt = DevBuf<>(nbuckets + 1);
   const size_t ntl = (size_t)(prm.S + 1) * grid_for(max_tasks);
@@ -422,11 +422,8 @@ MsmSortScratch::MsmSortScratch(size_t max_n_, size_t max_present, const MsmParam
   k = std::max(1, std::min(4, HS_STAGE / (HS_TPB * prm.windows)));
   if (k == 3) k = 2;
   const uint32_t nblk = (uint32_t)((max_n + k * HS_TPB - 1) / (k * HS_TPB));
-  const uint32_t max_tiles = (uint32_t)((max_entries + HS_TILE - 1) / HS_TILE + nbins);
-  const uint32_t nq = nbins << b2;
-  const uint32_t max_tiles3 = (uint32_t)((max_entries + HS_TILE - 1) / HS_TILE + nq);
-  const size_t nh3 = ((size_t)max_tiles3 << b3) + 1;
-  toff3 = DevBuf<>((size_t)nq + 1);
+  const size_t nh3 = (tiles3(max_entries) << b3) + 1;
+  toff3 = DevBuf<>((size_t)nq() + 1);
   // a shared build keeps HS_NPLAN count arrays, stride3 apart, whether or not every plan is there
   stride3 = nh3;
   const size_t nh3_all = nplans > 1 ? nh3 * HS_NPLAN : nh3;
@@ -434,30 +431,33 @@ MsmSortScratch::MsmSortScratch(size_t max_n_, size_t max_present, const MsmParam
   hist3 = DevBuf<>(nh3_all);
   off3 = DevBuf<>(nh3_all);
   if (nplans > 1) binbase = DevBuf<>(nbins + 1);
-  const size_t nh = (size_t)nbins * nblk, nh2 = (size_t)max_tiles << b2;
+  const size_t nh = (size_t)nbins * nblk, nh2 = tiles2(max_entries) << b2;
   hist = DevBuf<>(nh);
   blkoff = DevBuf<>(nh);
   toff = DevBuf<>(nbins + 1);
   hist2 = DevBuf<>(nh2);
   off2 = DevBuf<>(nh2);
-  subbase = DevBuf<>((size_t)nq + 1);
+  subbase = DevBuf<>((size_t)nq() + 1);
   ent_a = DevBuf<uint2>(max_entries);
   ent_b = DevBuf<uint2>(max_entries);
   const size_t scan_n = std::max(std::max(std::max(nbuckets + 1, nh3_all), std::max(nh2, ntl)), nh);
   tsum = DevBuf<>(scan_tiles_for(scan_n) + 1);
 }
 
+size_t MsmSortScratch::tiles2(size_t total) const { return (total + HS_TILE - 1) / HS_TILE + nbins; }
+size_t MsmSortScratch::tiles3(size_t total) const { return (total + HS_TILE - 1) / HS_TILE + nq(); }
+
 MsmPlan::MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream, size_t max_present,
                  std::shared_ptr<MsmSortScratch> scratch)
     : prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream), sc_(std::move(scratch)) {
   if (!sc_) sc_ = std::make_shared<MsmSortScratch>(max_n_, max_present, prm_);
   nbuckets_ = prm_.buckets();
-  max_entries_ = std::max<size_t>(std::min(max_present, max_n_), 1) * prm_.windows;
+  max_entries_ = prm_.max_entries(max_n_, max_present);
   const MsmParams& q = sc_->prm;
   if (q.c != prm_.c || q.windows != prm_.windows || q.depth != prm_.depth || q.S != prm_.S || sc_->max_n < max_n_ ||
       sc_->max_entries < max_entries_)
     throw std::runtime_error("MSM: sort scratch built for other parameters or fewer entries");
-  max_tasks_ = (max_entries_ + prm_.S - 1) / prm_.S + nbuckets_;
+  max_tasks_ = prm_.max_tasks(max_entries_);
   merge_levels_ = sc_->merge_levels;
   vals_sorted_ = DevBuf<>(max_entries_);
   bstart_ = DevBuf<>(nbuckets_ + 1);
@@ -469,20 +469,63 @@ MsmPlan::MsmPlan(size_t max_n, const MsmParams& prm, hipStream_t stream, size_t 
   ready_ = Event(false);
 }
 
-// pass A's kernels for K scalars per thread, with (MASK) or without a mask of finite bases
+namespace {
+
+// pass A's kernels for K scalars per thread, with (MASK) or without an index list of the scalars to
+// visit; TAG: every entry carries the plans it belongs to (a shared build)
 template <bool MASK>
-static auto hs_count1_for(int k) {
+auto hs_count1_for(int k) {
   return k == 4 ? k_hs_count1<4, MASK> : (k == 2 ? k_hs_count1<2, MASK> : k_hs_count1<1, MASK>);
 }
-template <bool MASK>
-static auto hs_scatter1_for(int k) {
-  return k == 4 ? k_hs_scatter1<4, MASK> : (k == 2 ? k_hs_scatter1<2, MASK> : k_hs_scatter1<1, MASK>);
+template <bool MASK, bool TAG>
+auto hs_scatter1_for(int k) {
+  return k == 4 ? k_hs_scatter1<4, MASK, TAG> : (k == 2 ? k_hs_scatter1<2, MASK, TAG> : k_hs_scatter1<1, MASK, TAG>);
 }
 
-template <bool MASK>
-static auto hs_scatter1_tagged_for(int k) {
-  return k == 4 ? k_hs_scatter1<4, MASK, true> : (k == 2 ? k_hs_scatter1<2, MASK, true> : k_hs_scatter1<1, MASK, true>);
+// Passes A and B of the three-pass LDS-staged bucket sort (hsort_kernels.hpp), enqueued on st.  Pass A
+// visits the m scalars that `index` lists (null: all n, m = n) and drops their zero digits; memb (a
+// shared build's membership table, null for one plan) tags every entry with its plans; skew takes the
+// wave-aggregated LDS claims of pass B (whole waves of one sub-bin: the 0/1-heavy witness).  Leaves
+// the entries by sub-bin in sc.ent_b, the sub-bins' bases in sc.subbase and the bins' in binbase
+// (nbins + 1 words, the last one the entry count).
+void sort_passes_ab(MsmSortScratch& sc, const uint32_t* scalars, size_t n, const uint32_t* index, size_t m,
+                    const uint8_t* memb, bool skew, uint32_t* binbase, hipStream_t st) {
+  const MsmParams& prm = sc.prm;
+  const int W = prm.windows, k = sc.k, b3 = sc.b3, sh1 = sc.b2 + b3;
+  const uint32_t nbins = sc.nbins, nsub = 1u << sc.b2;
+  const uint32_t nblk = (uint32_t)((m + k * HS_TPB - 1) / (k * HS_TPB));
+  uint2* ea = sc.ent_a;
+  // A: digits -> bins
+  auto count1 = index ? hs_count1_for<true>(k) : hs_count1_for<false>(k);
+  hipLaunchKernelGGL(count1, dim3(nblk), dim3(HS_TPB), 0, st, scalars, (uint32_t)n, index, (uint32_t)m, prm.c, W,
+                     prm.depth, sh1, nbins, sc.hist);
+  scan_nolookback(sc.hist, sc.blkoff, (size_t)nbins * nblk, sc.tsum, st);
+  hipLaunchKernelGGL(k_hs_binbase, dim3(1), dim3(512), 0, st, sc.blkoff, sc.hist, nbins, nblk, binbase, sc.toff);
+  auto scatter1 = memb ? (index ? hs_scatter1_for<true, true>(k) : hs_scatter1_for<false, true>(k))
+                       : (index ? hs_scatter1_for<true, false>(k) : hs_scatter1_for<false, false>(k));
+  const size_t lds1 = (size_t)k * HS_TPB * W * 8 + (size_t)nbins * 8;
+  hipLaunchKernelGGL(scatter1, dim3(nblk), dim3(HS_TPB), lds1, st, scalars, (uint32_t)n, index, (uint32_t)m, prm.c, W,
+                     prm.depth, sh1, nbins, sc.blkoff, ea, memb);
+  // B: bins -> sub-bins (tiles past the used ones exit; their counters stay zero)
+  const size_t tiles = sc.tiles2((uint32_t)(m * W)), nh2 = tiles << sc.b2;
+  HIPX(hipMemsetAsync(sc.hist2, 0, nh2 * 4, st));
+  hipLaunchKernelGGL((skew ? k_hs_count2<true> : k_hs_count2<false>), dim3((unsigned)tiles), dim3(HS_TPB), 0, st, ea,
+                     binbase, sc.toff, nbins, b3, nsub, sc.hist2);
+  scan_nolookback(sc.hist2, sc.off2, nh2, sc.tsum, st);
+  hipLaunchKernelGGL(k_hs_subbase, dim3(grid_for(sc.nq() + 1)), dim3(HS_TPB), 0, st, sc.off2, binbase, sc.toff, nbins,
+                     nsub, sc.subbase);
+  hipLaunchKernelGGL((skew ? k_hs_scatter2<true, false> : k_hs_scatter2<false, false>), dim3((unsigned)tiles),
+                     dim3(HS_TPB), 0, st, ea, binbase, sc.toff, nbins, b3, nsub, sc.off2, sc.ent_b.get(), nullptr);
 }
+
+// the opening of the tiled pass C (pass B one level down: no workgroup takes more than HS_TILE
+// entries): the sub-bins' tile offsets and `words` zeroed counters for the sc.tiles3() tiles
+void open_tiled_pass_c(MsmSortScratch& sc, size_t words, hipStream_t st) {
+  hipLaunchKernelGGL(k_hs_subtiles, dim3(1), dim3(SC_TPB), 0, st, sc.subbase, sc.nq(), sc.toff3);
+  HIPX(hipMemsetAsync(sc.hist3, 0, words * 4, st));
+}
+
+}  // namespace
 
 void MsmPlan::build(const uint32_t* scalars, size_t n, const uint32_t* present, size_t n_present) {
   if (n > max_n_) throw std::runtime_error("MSM: n exceeds plan capacity");
@@ -491,69 +534,37 @@ void MsmPlan::build(const uint32_t* scalars, size_t n, const uint32_t* present, 
   if (n_present * prm_.windows > max_entries_) throw std::runtime_error("MSM: finite bases exceed plan capacity");
   n_ = n;
   MsmSortScratch& sc = *sc_;
-  const uint32_t W = (uint32_t)prm_.windows;
-  const uint32_t nb = (uint32_t)nbuckets_;
-  const int hs_b2_ = sc.b2, hs_b3_ = sc.b3;
-  const uint32_t hs_nbins_ = sc.nbins;
+  const uint32_t nb = (uint32_t)nbuckets_, nq = sc.nq();
+  const int b3 = sc.b3;
   hipStream_t st = stream_;
   // total_ = n * W (with a mask: its count * W) bounds the nonzero digits (the accumulate grid: threads
   // past the last task exit), so nothing waits on the host; the exact count stays on the device
   // (entries_dev)
-  total_ = (uint32_t)(n_present * W);
+  total_ = (uint32_t)(n_present * prm_.windows);
   hs_built_ = false;
   if (total_ != 0) {
-    // the hand-written three-pass LDS-staged bucket sort (hsort_kernels.hpp), zero digits and the
-    // scalars whose base is at infinity dropped in pass A (it visits only the mask's index list).  Dense plans (uniform scalars: the H MSM) group their sub-bins with one workgroup each
-    // (k_hs_fine); compacted plans (the witness: whole waves of one bin / sub-bin / bucket) take the
-    // wave-aggregated LDS claims and the tiled pass C, as do keys with more than 5 bucket bits per
-    // sub-bin
-    const int k = sc.k;
-    // pass A visits the scalars the mask lists (all n without one)
-    const uint32_t nblk = (uint32_t)((n_present + k * HS_TPB - 1) / (k * HS_TPB)), nsub = 1u << hs_b2_;
-    const int sh1 = hs_b2_ + hs_b3_;
-    uint2* ea = sc.ent_a;
-    uint2* eb = sc.ent_b;
-    // A: digits -> bins
-    auto count1 = present ? hs_count1_for<true>(k) : hs_count1_for<false>(k);
-    hipLaunchKernelGGL(count1, dim3(nblk), dim3(HS_TPB), 0, st, scalars, (uint32_t)n, present,
-                       (uint32_t)n_present, prm_.c, (int)W, prm_.depth, sh1, hs_nbins_, sc.hist);
-    scan_nolookback(sc.hist, sc.blkoff, (size_t)hs_nbins_ * nblk, sc.tsum, st);
-    hipLaunchKernelGGL(k_hs_binbase, dim3(1), dim3(512), 0, st, sc.blkoff, sc.hist, hs_nbins_, nblk, hs_binbase_,
-                       sc.toff);
-    auto scatter1 = present ? hs_scatter1_for<true>(k) : hs_scatter1_for<false>(k);
-    const size_t lds1 = (size_t)k * HS_TPB * W * 8 + (size_t)hs_nbins_ * 8;
-    hipLaunchKernelGGL(scatter1, dim3(nblk), dim3(HS_TPB), lds1, st, scalars, (uint32_t)n, present,
-                       (uint32_t)n_present, prm_.c, (int)W, prm_.depth, sh1, hs_nbins_, sc.blkoff, ea,
-                       (const uint8_t*)nullptr);
-    // B: bins -> sub-bins (tiles past the used ones exit; their counters stay zero)
-    const size_t tiles = ((size_t)total_ + HS_TILE - 1) / HS_TILE + hs_nbins_;
-    const size_t nh2 = tiles << hs_b2_;
-    HIPX(hipMemsetAsync(sc.hist2, 0, nh2 * 4, st));
-    const bool skew = !dense_;
-    hipLaunchKernelGGL((skew ? k_hs_count2<true> : k_hs_count2<false>), dim3((unsigned)tiles), dim3(HS_TPB), 0, st, ea,
-                       hs_binbase_, sc.toff, hs_nbins_, hs_b3_, nsub, sc.hist2);
-    scan_nolookback(sc.hist2, sc.off2, nh2, sc.tsum, st);
-    const uint32_t nq = hs_nbins_ * nsub;
-    hipLaunchKernelGGL(k_hs_subbase, dim3(grid_for(nq + 1)), dim3(HS_TPB), 0, st, sc.off2, hs_binbase_, sc.toff,
-                       hs_nbins_, nsub, sc.subbase);
-    hipLaunchKernelGGL((skew ? k_hs_scatter2<true, false> : k_hs_scatter2<false, false>), dim3((unsigned)tiles),
-                       dim3(HS_TPB), 0, st, ea, hs_binbase_, sc.toff, hs_nbins_, hs_b3_, nsub, sc.off2, eb, nullptr);
+    // zero digits and the scalars whose base is at infinity are dropped in pass A (it visits only the
+    // mask's index list).  Dense plans (uniform scalars: the H MSM) group their sub-bins with one
+    // workgroup each (k_hs_fine); compacted plans (the witness: whole waves of one bin / sub-bin /
+    // bucket) take the wave-aggregated LDS claims and the tiled pass C, as do keys with more than 5
+    // bucket bits per sub-bin
+    sort_passes_ab(sc, scalars, n, present, n_present, nullptr, !dense_, hs_binbase_, st);
+    const uint2* eb = sc.ent_b;
     // C: sub-bins -> buckets, bounds and task counts
-    if (dense_ && hs_b3_ <= HS_B3) {
-      hipLaunchKernelGGL(k_hs_fine, dim3(nq), dim3(HS_FINE_TPB), 0, st, eb, sc.subbase, nq, hs_b3_, nb,
-                         (uint32_t)prm_.S, vals_sorted_, bstart_, bend_, sc.cnt);
-    } else {  // tiled: pass B one level down (no workgroup takes more than HS_TILE entries)
-      const uint32_t nf = 1u << hs_b3_;
-      hipLaunchKernelGGL(k_hs_subtiles, dim3(1), dim3(SC_TPB), 0, st, sc.subbase, nq, sc.toff3);
-      const size_t tiles3 = ((size_t)total_ + HS_TILE - 1) / HS_TILE + nq, nh3 = tiles3 << hs_b3_;
-      HIPX(hipMemsetAsync(sc.hist3, 0, nh3 * 4, st));
+    if (dense_ && b3 <= HS_B3) {
+      hipLaunchKernelGGL(k_hs_fine, dim3(nq), dim3(HS_FINE_TPB), 0, st, eb, sc.subbase, nq, b3, nb, (uint32_t)prm_.S,
+                         vals_sorted_, bstart_, bend_, sc.cnt);
+    } else {
+      const uint32_t nf = 1u << b3;
+      const size_t tiles3 = sc.tiles3(total_), nh3 = tiles3 << b3;
+      open_tiled_pass_c(sc, nh3, st);
       hipLaunchKernelGGL(k_hs_count2<true>, dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, sc.subbase, sc.toff3, nq,
                          0, nf, sc.hist3);
       scan_nolookback(sc.hist3, sc.off3, nh3, sc.tsum, st);
       hipLaunchKernelGGL((k_hs_scatter2<true, true>), dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, sc.subbase,
                          sc.toff3, nq, 0, nf, sc.off3, nullptr, vals_sorted_);
       hipLaunchKernelGGL(k_hs_bounds3, dim3(grid_for((size_t)nb + 1)), dim3(HS_TPB), 0, st, sc.toff3, sc.off3,
-                         sc.subbase, hs_b3_, nb, (uint32_t)prm_.S, bstart_, bend_, sc.cnt);
+                         sc.subbase, b3, nb, (uint32_t)prm_.S, bstart_, bend_, sc.cnt);
     }
     hs_built_ = true;
   }
@@ -572,7 +583,7 @@ void MsmPlan::build_tail(bool empty) {
   // accumulate-task offsets and the heavy-bucket merge levels' offsets (look-back-free scans: they
   // run beside the accumulations of the other streams)
   scan_nolookback(sc.cnt, off_task_, nbuckets_ + 1, sc.tsum, st);
-  max_tasks_now_ = ((size_t)total_ + prm_.S - 1) / prm_.S + nbuckets_;
+  max_tasks_now_ = prm_.max_tasks(total_);
   if (total_ > 0) {
     // accumulate-task order by length, longest first
     const unsigned nblk = grid_for(max_tasks_now_);
@@ -625,38 +636,15 @@ void MsmPlan::build_shared(MsmPlan* const plans[PlanMembership::NPLAN], const ui
   if (pmask) {
     // passes A and B as in build(), over the union of the plans' scalars and with the plans' tag in
     // every entry; pass C (tiled) per plan
-    const uint32_t W = (uint32_t)prm.windows, nb = (uint32_t)first->nbuckets_;
-    const int b2 = sc.b2, b3 = sc.b3, k = sc.k, sh1 = b2 + b3;
-    const uint32_t nbins = sc.nbins, nsub = 1u << b2, nf = 1u << b3;
-    const uint32_t total = (uint32_t)(n_any * W);
-    const uint32_t nblk = (uint32_t)((n_any + k * HS_TPB - 1) / (k * HS_TPB));
-    uint2* ea = sc.ent_a;
-    uint2* eb = sc.ent_b;
-    auto count1 = index ? hs_count1_for<true>(k) : hs_count1_for<false>(k);
-    hipLaunchKernelGGL(count1, dim3(nblk), dim3(HS_TPB), 0, st, scalars, (uint32_t)n, index, (uint32_t)n_any, prm.c,
-                       (int)W, prm.depth, sh1, nbins, sc.hist);
-    scan_nolookback(sc.hist, sc.blkoff, (size_t)nbins * nblk, sc.tsum, st);
-    hipLaunchKernelGGL(k_hs_binbase, dim3(1), dim3(512), 0, st, sc.blkoff, sc.hist, nbins, nblk, sc.binbase, sc.toff);
-    auto scatter1 = index ? hs_scatter1_tagged_for<true>(k) : hs_scatter1_tagged_for<false>(k);
-    const size_t lds1 = (size_t)k * HS_TPB * W * 8 + (size_t)nbins * 8;
-    hipLaunchKernelGGL(scatter1, dim3(nblk), dim3(HS_TPB), lds1, st, scalars, (uint32_t)n, index, (uint32_t)n_any,
-                       prm.c, (int)W, prm.depth, sh1, nbins, sc.blkoff, ea, mem.memb.get());
-    const size_t tiles = ((size_t)total + HS_TILE - 1) / HS_TILE + nbins;
-    const size_t nh2 = tiles << b2;
-    HIPX(hipMemsetAsync(sc.hist2, 0, nh2 * 4, st));
-    hipLaunchKernelGGL(k_hs_count2<true>, dim3((unsigned)tiles), dim3(HS_TPB), 0, st, ea, sc.binbase, sc.toff, nbins, b3,
-                       nsub, sc.hist2);
-    scan_nolookback(sc.hist2, sc.off2, nh2, sc.tsum, st);
-    const uint32_t nq = nbins * nsub;
-    hipLaunchKernelGGL(k_hs_subbase, dim3(grid_for(nq + 1)), dim3(HS_TPB), 0, st, sc.off2, sc.binbase, sc.toff, nbins,
-                       nsub, sc.subbase);
-    hipLaunchKernelGGL((k_hs_scatter2<true, false>), dim3((unsigned)tiles), dim3(HS_TPB), 0, st, ea, sc.binbase, sc.toff,
-                       nbins, b3, nsub, sc.off2, eb, nullptr);
-    hipLaunchKernelGGL(k_hs_subtiles, dim3(1), dim3(SC_TPB), 0, st, sc.subbase, nq, sc.toff3);
+    sort_passes_ab(sc, scalars, n, index, n_any, mem.memb.get(), true, sc.binbase, st);
+    const uint32_t nb = (uint32_t)first->nbuckets_, nq = sc.nq(), nbins = sc.nbins;
+    const int b3 = sc.b3;
+    const uint32_t nf = 1u << b3;
+    const uint2* eb = sc.ent_b;
     // every plan's array: its tiles' counts and one word more (k_hs_count3), all scanned as one
-    const size_t tiles3 = ((size_t)total + HS_TILE - 1) / HS_TILE + nq, stride = (tiles3 << b3) + 1;
+    const size_t tiles3 = sc.tiles3((uint32_t)(n_any * prm.windows)), stride = (tiles3 << b3) + 1;
     if (stride > sc.stride3) throw std::runtime_error("MSM: sort scratch too small for this shared build");
-    HIPX(hipMemsetAsync(sc.hist3, 0, stride * HS_NPLAN * 4, st));
+    open_tiled_pass_c(sc, stride * HS_NPLAN, st);
     hipLaunchKernelGGL(k_hs_count3, dim3((unsigned)tiles3), dim3(HS_TPB), 0, st, eb, sc.subbase, sc.toff3, nq, nf, pmask,
                        stride, sc.hist3);
     scan_nolookback(sc.hist3, sc.off3, stride * HS_NPLAN, sc.tsum, st);
@@ -685,7 +673,7 @@ MsmEngine::MsmEngine(Curve curve, const MsmParams& prm, size_t max_n, hipStream_
     : curve_(curve), prm_(prm), max_n_(std::max<size_t>(max_n, 1)), stream_(stream) {
   fwords_ = curve_fwords(curve);
   nbuckets_ = prm_.buckets();
-  max_tasks_ = (max_n_ * prm_.windows + prm_.S - 1) / prm_.S + nbuckets_;
+  max_tasks_ = prm_.max_tasks(max_n_ * prm_.windows);
   const size_t xyzz_words = 4 * (size_t)fwords_;
   part_a_ = DevBuf<>(max_tasks_ * xyzz_words);
   part_b_ = DevBuf<>(max_tasks_ * xyzz_words);

@@ -23,6 +23,8 @@
 //                 the offsets of the heavy-bucket merge levels.
 //     Plans over the same scalars that differ only in their masks (a proof's witness plans B, A, C)
 //     come from one build_shared: steps 1 and 2 once over the union, the entries tagged by plan.
+//     build and build_shared enqueue the sort's first two passes (digits -> bins -> sub-bins) through
+//     one driver in msm.hip; only the last pass (sub-bins -> buckets, bounds) differs between them.
 //
 //  MsmEngine (per curve and stream: partial sums, buckets, reduction tree)
 //     4. accumulate: one thread per task, mixed XYZZ additions of gathered bases;
@@ -41,6 +43,7 @@
 //                 (2^(c T g)) weights by Horner (msm_fold).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -51,6 +54,13 @@
 #include "hip_raii.hpp"
 
 namespace zkp {
+
+// the rounded-up base-2 logarithm: the least l with 2^l >= n (0 for n <= 1)
+inline int lg_ceil(size_t n) {
+  int l = 0;
+  while ((size_t(1) << l) < n) ++l;
+  return l;
+}
 
 struct MsmParams {
   int c = 16;        // window bits
@@ -72,8 +82,7 @@ struct MsmParams {
     MsmParams p;
     if (scalar_bits < 1 || scalar_bits > 255) throw std::invalid_argument("MSM scalar bits must be within 1..255");
     p.scalar_bits = scalar_bits;
-    int lg = 0;
-    while ((size_t(1) << lg) < n) ++lg;
+    const int lg = lg_ceil(n);
     // one bucket set of 2^(c-1) buckets against n*W entries: c = lg - 4 keeps every bucket ~8*W
     // entries deep and the bucket reduction (2^c full adds) small; 20 bits caps the automatic choice
     p.c = c_override > 0 ? c_override : (lg - 4 < MIN_C ? MIN_C : (lg - 4 > 20 ? 20 : lg - 4));
@@ -88,6 +97,12 @@ struct MsmParams {
   }
   size_t half() const { return size_t(1) << (c - 1); }
   size_t buckets() const { return (size_t)groups * half(); }
+  // capacities: the entries of max_n scalars of which at most max_present emit digits, and the
+  // accumulate tasks of so many entries (every bucket's last task may be a short one)
+  size_t max_entries(size_t max_n, size_t max_present) const {
+    return std::max<size_t>(std::min(max_present, max_n), 1) * windows;
+  }
+  size_t max_tasks(size_t entries) const { return (entries + S - 1) / S + buckets(); }
   // a group's buckets as U rows of V: bucket k = u V + v, V = 2^ceil((c-1)/2) >= U
   int lgV() const { return c / 2; }
   int V() const { return 1 << lgV(); }
@@ -95,7 +110,7 @@ struct MsmParams {
   // every group reduces to two sub-groups of V points (its row sums, then its column sums), each of
   // which leaves lgP subset sums Q_b and sum_p T_p (P = V / M segments): K points
   int subgroups() const { return 2 * groups; }
-  int lg_m() const { int l = 0; while ((1 << l) < M) ++l; return l; }
+  int lg_m() const { return lg_ceil((size_t)M); }
   int lgP() const { return lgV() - lg_m(); }
   int K() const { return lgP() + 1; }
   size_t out_points() const { return (size_t)subgroups() * K(); }
@@ -118,6 +133,9 @@ inline int dense_window_bits(int c, size_t n) {
   }
   return c;
 }
+// the automatic window bits of a plan over n uniform scalars (the prover's H plan, the kernel-level
+// MSMs, the ptau sums): lg n - 3 within [8, 20], moved off a collapsed top window
+inline int h_window_bits(size_t n) { return dense_window_bits(std::min(20, std::max(8, lg_ceil(n) - 3)), n); }
 
 // words per coordinate element: G1 -> Fq (8 words), G2 -> Fq2 (16 words)
 enum class Curve { G1 = 1, G2 = 2 };
@@ -210,6 +228,11 @@ struct MsmSortScratch {
   int merge_levels = 0;
   int b2 = 0, b3 = 0, k = 1;  // sub-bin / bucket bits of the key, scalars per thread in pass A
   uint32_t nbins = 0;
+  uint32_t nq() const { return nbins << b2; }  // sub-bins
+  // workgroups (tiles) of pass B and of the tiled pass C over `total` entries: every bin / sub-bin may
+  // end in a partial tile
+  size_t tiles2(size_t total) const;
+  size_t tiles3(size_t total) const;
   DevBuf<> cnt, tl_hist, tl_off, lvl_tsum;
   DevBuf<> toff3, hist3, off3;
   DevBuf<> hist, blkoff, toff, hist2, off2, subbase;

@@ -69,12 +69,6 @@ void require_free(size_t bytes) {
                                               " MiB does not fit in " + std::to_string(free_b >> 20) + " MiB of free HBM");
 }
 
-int lg_ceil(size_t n) {
-  int lg = 0;
-  while ((size_t(1) << lg) < n) ++lg;
-  return lg;
-}
-
 // one sum per base set
 struct Sum {
   Jac<HFq> g1 = Jac<HFq>::inf();
@@ -91,8 +85,7 @@ class SumRunner {
  public:
   SumRunner(size_t max_n, int scalar_bits, bool g2, hipStream_t st, Spans& sp, PtauVerifyTimings& t)
       : st_(st), sp_(sp), t_(t), ch_(std::max<size_t>(1, std::min(max_n, verify_chunk_points()))) {
-    const int c = scalar_bits == 129 ? rlc_window_bits(ch_)
-                                     : dense_window_bits(std::min(20, std::max(8, lg_ceil(ch_) - 3)), ch_);
+    const int c = scalar_bits == 129 ? rlc_window_bits(ch_) : h_window_bits(ch_);
     prm_ = make_params(ch_, c, 1, scalar_bits);
     const MsmOptions opt = msm_options();
     apply_task_options(prm_, opt.task_h, opt);
