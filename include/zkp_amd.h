@@ -443,8 +443,8 @@ zkp_status zkp_bench_ntt_batch(int device, int log_n, int count, int warmup, int
 
 /* ---- Phase 1 from its start: `snarkjs powersoftau new | contribute | beacon` (reference
  * circuit/scripts/generate_keys_phase1.sh:6,8,10,18).  With zkp_ptau_verify and zkp_ptau_prepare_phase2 the
- * script's commands run here end to end, except `export challenge`, `challenge contribute` and `import
- * response` (script lines 12-14: the challenge-file format is another restatement, left for later).  The
+ * script's commands run here end to end; `export challenge`, `challenge contribute` and `import response`
+ * (script lines 12-14) follow below.  The
  * formats are restated from snarkjs 0.4.22 (parity unpinned); tests/helpers/ptau_model.py fixes them byte for
  * byte.  Buffers handed out are released with zkp_buffer_free.
  *
@@ -484,6 +484,74 @@ zkp_status zkp_ptau_beacon(int device, const uint8_t* ptau, size_t len, const ui
 zkp_status zkp_ptau_contribute_timings(double* ms, int n);
 zkp_status zkp_points_scale_powers(int device, int g2, const uint8_t* points, size_t n, const uint8_t* first32,
                                    const uint8_t* ratio32, uint8_t* out);
+
+/* ---- The third-party path of phase 1: `snarkjs powersoftau export challenge | challenge contribute | import
+ * response` (reference circuit/scripts/generate_keys_phase1.sh:12-14): a contributor works on a challenge file
+ * and returns a response file, and never holds the ptau.  With these the reference's phase-1 script runs here
+ * from its first line to its last.  Formats restated from snarkjs 0.4.22 (parity unpinned);
+ * tests/helpers/ptau_challenge_model.py fixes them byte for byte.  N = 2^power.
+ *   challenge file  384 N + 128 bytes: the last record's response hash (Blake2b-512 of "" for a file without
+ *                   contributions), then tauG1 (2N - 1 points), tauG2 (N), alphaTauG1 (N), betaTauG1 (N), betaG2
+ *                   (1), uncompressed (big-endian standard form, x then y, G2 c1 before c0; 0x40 then zeros:
+ *                   infinity).  Blake2b-512 of the whole file is the challenge.
+ *   response file   192 N + 864 bytes: the challenge hash, the five sections after the contribution compressed
+ *                   (big-endian x; 0x80 in the first byte: y is the greater root), the contributor's public key
+ *                   uncompressed (768 bytes).  Blake2b-512 of the whole file is the response hash.
+ * Everything that can be refused is refused before the device is touched.  ZKP_PTAU_CHUNK as above.
+ *
+ * zkp_ptau_export_challenge: sections 1-7 are checked as by zkp_ptau_contribute (the header, the sizes, the
+ * records of section 7); a truncated file (power < ceremonyPower) is ZKP_ERR_INVALID_ARG for the same reason.
+ * The points are not checked one by one: the hash below vouches for them.  The file is hashed as it is written, and if the
+ * hash is not the challenge that section 7 implies (the last record's nextChallenge, or the first challenge of
+ * the ceremony) the call fails with ZKP_ERR_FORMAT "ptau: sections 2-6 do not hash to the last contribution's
+ * nextChallenge" and returns no file.  snarkjs only logs this; here a challenge that is not the chain's would
+ * yield a response that zkp_ptau_import_response refuses anyway.
+ *
+ * zkp_ptau_challenge_contribute: the power is read from the length ((len - 128) / 384 a power of two within
+ * 2^1..2^28, else ZKP_ERR_FORMAT).  The key is drawn as by zkp_ptau_contribute (same rng, same order) and
+ * answers the hash of the challenge file.  Every point must have its coordinates below p (infinity: 0x40 then
+ * zeros) and be on its curve, else ZKP_ERR_FORMAT "challenge: section <id> point <i> is not on the curve"
+ * (checked on the device; smallest id, then smallest i).  Output: the response file.
+ *
+ * zkp_ptau_import_response: the old file is checked as above (truncated: ZKP_ERR_INVALID_ARG).  The response
+ * must have the length the old file's power gives (ZKP_ERR_FORMAT "response: size of the contribution is
+ * invalid"), begin with the old file's last challenge (ZKP_ERR_FORMAT "response: this contribution is not based
+ * on the previous hash") and hold a key of nine canonical points on their curves (ZKP_ERR_FORMAT "response: key
+ * point <k> ..."), all checked on the host.  Every compressed point is then decompressed on the device (one
+ * square root each, in Fq or Fq2): 0x40 with anything but zeros beside it, an x >= p or an x for which x^3 + b
+ * is a non-residue is ZKP_ERR_FORMAT "response: section <id> point <i> is not a point of the curve".  A type-0
+ * record is appended to section 7 (name: recorded unless NULL).  Output: sections 1-7; sections 12-15 are
+ * dropped, as by zkp_ptau_contribute.  The same-ratio checks of the contribution are NOT run here:
+ * zkp_ptau_verify does that on the result, as in snarkjs.  Through export, challenge contribute and import the
+ * result equals zkp_ptau_contribute's with the same rand64, entropy and name byte for byte.
+ *
+ * zkp_ptau_challenge_timings: ms of the calling thread's last call of the three: [0] total, [1] parse + point
+ * check, [2] the challenge hash (export / import: the first challenge of a file without contributions),
+ * [3] key draw / key check, [4] upload, [5] decoding, [6] G1 decompression, [7] G2 decompression, [8] G1
+ * scaling, [9] G2 scaling, [10] encoding, [11] download, [12] the hash threads, [13] chunks.
+ *
+ * Device parts, each on its own (kernel-level):
+ * zkp_points_decompress: n compressed points (G1 32 bytes, G2 64) -> the zkey layout (out_lem: n x 64 / 128
+ * bytes).  A refused point (as in import) is written as zeros; *n_bad counts them and *first_bad is the
+ * smallest such index (all ones if none).  A G2 point on the twist but outside the subgroup is not refused.
+ * zkp_points_from_uncompressed: n uncompressed points (G1 64 bytes, G2 128) -> the zkey layout with the same
+ * two counts; refused: a coordinate >= p, 0x40 set and anything but zeros beside it.  Whether the point is on
+ * its curve is zkp_points_check's question.
+ * zkp_field_sqrt: n elements of Fq (fq2 = 0: 32 bytes LE, standard form) or Fq2 (64 bytes: c0 then c1); a
+ * coordinate >= p is ZKP_ERR_INVALID_ARG.  out: a root of each in the same form (which of the two is
+ * unspecified), or zeros; is_square: one byte per element. */
+zkp_status zkp_ptau_export_challenge(int device, const uint8_t* ptau, size_t len, uint8_t** out, size_t* out_len);
+zkp_status zkp_ptau_challenge_contribute(int device, const uint8_t* challenge, size_t len,
+                                         const uint8_t* rand64 /* NULL: OS CSPRNG */, const char* entropy, uint8_t** out,
+                                         size_t* out_len);
+zkp_status zkp_ptau_import_response(int device, const uint8_t* ptau, size_t len, const uint8_t* response, size_t response_len,
+                                    const char* name, uint8_t** out, size_t* out_len);
+zkp_status zkp_ptau_challenge_timings(double* ms, int n);
+zkp_status zkp_points_decompress(int device, int g2, const uint8_t* compressed, size_t n, uint8_t* out_lem, uint64_t* n_bad,
+                                 uint64_t* first_bad);
+zkp_status zkp_points_from_uncompressed(int device, int g2, const uint8_t* bytes, size_t n, uint8_t* out_lem, uint64_t* n_bad,
+                                        uint64_t* first_bad);
+zkp_status zkp_field_sqrt(int device, int fq2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* is_square);
 
 #ifdef __cplusplus
 }

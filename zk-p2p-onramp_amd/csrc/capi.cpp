@@ -25,6 +25,7 @@
 #include "host_pairing.hpp"
 #include "mpc.hpp"
 #include "prover.hpp"
+#include "ptau_challenge.hpp"
 #include "ptau_contribute.hpp"
 #include "ptau_verify.hpp"
 #include "zkey_io.hpp"
@@ -530,6 +531,60 @@ zkp_status zkp_points_scale_powers(int device, int g2, const uint8_t* points, si
                                    const uint8_t* ratio32, uint8_t* out) {
   if ((n && (!points || !out)) || !first32 || !ratio32) return fail(ZKP_ERR_INVALID_ARG, "null argument");
   return guard([&] { zkp::points_scale_powers(device, g2 != 0, points, n, first32, ratio32, out); });
+}
+
+zkp_status zkp_ptau_export_challenge(int device, const uint8_t* ptau, size_t len, uint8_t** out, size_t* out_len) {
+  if (!ptau || !len || !out || !out_len) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] { buf = zkp::ptau_export_challenge(device, ptau, len); });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_ptau_challenge_contribute(int device, const uint8_t* challenge, size_t len, const uint8_t* rand64,
+                                         const char* entropy, uint8_t** out, size_t* out_len) {
+  if (!challenge || !len || !entropy || !out || !out_len) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] {
+    zkp::ChaChaRng rng = entropy_rng(rand64, entropy);
+    buf = zkp::ptau_challenge_contribute(device, challenge, len, rng);
+  });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_ptau_import_response(int device, const uint8_t* ptau, size_t len, const uint8_t* response, size_t response_len,
+                                    const char* name, uint8_t** out, size_t* out_len) {
+  if (!ptau || !len || !response || !response_len || !out || !out_len)
+    return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] { buf = zkp::ptau_import_response(device, ptau, len, response, response_len, name); });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_ptau_challenge_timings(double* ms, int n) {
+  if (!ms || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const zkp::PtauChallengeTimings t = zkp::ptau_challenge_timings();
+  const double v[14] = {t.total_ms,     t.parse_check_ms, t.challenge_ms, t.key_ms,    t.upload_ms,
+                        t.decode_ms,    t.decomp_g1_ms,   t.decomp_g2_ms, t.g1_ms,     t.g2_ms,
+                        t.encode_ms,    t.download_ms,    t.partial_hash_ms + t.next_challenge_ms, (double)t.chunks};
+  for (int i = 0; i < n && i < 14; ++i) ms[i] = v[i];
+  return ZKP_OK;
+}
+
+zkp_status zkp_points_decompress(int device, int g2, const uint8_t* compressed, size_t n, uint8_t* out_lem, uint64_t* n_bad,
+                                 uint64_t* first_bad) {
+  if ((n && (!compressed || !out_lem)) || !n_bad || !first_bad) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::points_decompress(device, g2 != 0, compressed, n, out_lem, n_bad, first_bad); });
+}
+
+zkp_status zkp_points_from_uncompressed(int device, int g2, const uint8_t* bytes, size_t n, uint8_t* out_lem, uint64_t* n_bad,
+                                        uint64_t* first_bad) {
+  if ((n && (!bytes || !out_lem)) || !n_bad || !first_bad) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::points_from_uncompressed(device, g2 != 0, bytes, n, out_lem, n_bad, first_bad); });
+}
+
+zkp_status zkp_field_sqrt(int device, int fq2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* is_square) {
+  if (n && (!in || !out || !is_square)) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::field_sqrt(device, fq2 != 0, in, n, out, is_square); });
 }
 
 zkp_status zkp_g2_subgroup_check(int device, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad) {

@@ -1147,22 +1147,99 @@ bool ptau_last_challenge(const uint8_t* sec7, size_t len, uint8_t out[64]) {
 
 void ptau_first_challenge(uint32_t ceremony_power, uint8_t out[64]) { first_challenge(ceremony_power, out); }
 
+bool ptau_last_hashes(const uint8_t* sec7, size_t len, uint8_t challenge[64], uint8_t response[64]) {
+  const std::vector<PtauContribution> cs = read_ptau_contributions(sec7, len);
+  if (cs.empty()) return false;
+  std::memcpy(challenge, cs.back().next_challenge, 64);
+  std::memcpy(response, cs.back().response_hash, 64);
+  return true;
+}
+
+namespace {
+
+// the key's nine points in the record's order (g1_s, g1_sx per secret, then the three g2_spx) in both forms
+void key_forms(const Affine<HFq> (&g1)[6], const Affine<HFq2> (&g2)[3], uint8_t lem[768], uint8_t u[768]) {
+  std::vector<uint8_t> l;
+  for (int k = 0; k < 6; ++k) put_g1_lem(l, g1[k]), g1_u(g1[k], u + 64 * k);
+  for (int k = 0; k < 3; ++k) put_g2_lem(l, g2[k]), g2_u(g2[k], u + 384 + 128 * k);
+  std::memcpy(lem, l.data(), 768);
+}
+
+// 32 big-endian bytes, standard form, below p
+bool fq_from_be(const uint8_t* p, HFq& out) {
+  uint8_t le[32];
+  for (int i = 0; i < 32; ++i) le[i] = p[31 - i];
+  const U256 v = host::u256_from_le(le);
+  if (host::u256_geq(v, host::FQ_DESC.mod)) return false;
+  out = HFq::from_std(v);
+  return true;
+}
+// an uncompressed point of n coordinates' worth of bytes: 0x40 then zeros, or no flag bit at all
+bool inf_from_u(const uint8_t* p, size_t n, bool& inf) {
+  inf = (p[0] & 0x40) != 0;
+  return !inf || (p[0] == 0x40 && zero_bytes(p + 1, n - 1));
+}
+
+}  // namespace
+
+void ptau_key_forms(const PtauDraw& d, const uint8_t challenge[64], uint8_t key_lem[768], uint8_t key_u[768]) {
+  Affine<HFq> g1[6];
+  Affine<HFq2> g2[3];
+  for (int k = 0; k < 3; ++k) {
+    g1[2 * k] = d.g1_s[k], g1[2 * k + 1] = d.g1_sx[k];
+    g2[k] = g2_times(key_g2_sp(k, challenge, d.g1_s[k], d.g1_sx[k]), d.prv[k]);
+  }
+  key_forms(g1, g2, key_lem, key_u);
+}
+
+void ptau_key_from_uncompressed(const uint8_t key_u[768], uint8_t key_lem[768]) {
+  auto bad = [](int k, const char* what) {
+    return ZkpError(ZKP_ERR_FORMAT, "response: key point " + std::to_string(k) + " " + what);
+  };
+  Affine<HFq> g1[6];
+  Affine<HFq2> g2[3];
+  for (int k = 0; k < 6; ++k) {
+    const uint8_t* p = key_u + 64 * k;
+    Affine<HFq>& a = g1[k];
+    a = Affine<HFq>{HFq::zero(), HFq::zero(), false};
+    if (!inf_from_u(p, 64, a.inf)) throw bad(k, "is not canonical");
+    if (a.inf) continue;
+    if (!fq_from_be(p, a.x) || !fq_from_be(p + 32, a.y)) throw bad(k, "is not canonical");
+    if (!host::g1_on_curve(a)) throw bad(k, "is not on the curve");
+  }
+  for (int k = 0; k < 3; ++k) {
+    const uint8_t* p = key_u + 384 + 128 * k;
+    Affine<HFq2>& a = g2[k];
+    a = Affine<HFq2>{HFq2::zero(), HFq2::zero(), false};
+    if (!inf_from_u(p, 128, a.inf)) throw bad(6 + k, "is not canonical");
+    if (a.inf) continue;
+    if (!fq_from_be(p, a.x.c1) || !fq_from_be(p + 32, a.x.c0) || !fq_from_be(p + 64, a.y.c1) || !fq_from_be(p + 96, a.y.c0))
+      throw bad(6 + k, "is not canonical");
+    if (!host::g2_on_curve(a)) throw bad(6 + k, "is not on the curve");
+  }
+  uint8_t again[768];
+  key_forms(g1, g2, key_lem, again);
+}
+
 std::vector<uint8_t> ptau_record(const PtauDraw& d, const uint8_t challenge[64], const uint8_t points_lem[448],
                                  const Blake2b& partial, uint32_t type, const char* name, const uint8_t* beacon,
                                  size_t beacon_len, uint32_t num_iterations_exp, uint8_t response_hash[64]) {
+  uint8_t key_lem[768], key_u[768];
+  ptau_key_forms(d, challenge, key_lem, key_u);
+  return ptau_record_of_key(key_lem, key_u, points_lem, partial, type, name, beacon, beacon_len, num_iterations_exp,
+                            response_hash);
+}
+
+std::vector<uint8_t> ptau_record_of_key(const uint8_t key_lem[768], const uint8_t key_u[768], const uint8_t points_lem[448],
+                                        const Blake2b& partial, uint32_t type, const char* name, const uint8_t* beacon,
+                                        size_t beacon_len, uint32_t num_iterations_exp, uint8_t response_hash[64]) {
   std::vector<uint8_t> rec(points_lem, points_lem + 448);
-  Affine<HFq2> g2_spx[3];
-  for (int k = 0; k < 3; ++k) {
-    g2_spx[k] = g2_times(key_g2_sp(k, challenge, d.g1_s[k], d.g1_sx[k]), d.prv[k]);
-    put_g1_lem(rec, d.g1_s[k]), put_g1_lem(rec, d.g1_sx[k]);
-  }
-  for (int k = 0; k < 3; ++k) put_g2_lem(rec, g2_spx[k]);
+  rec.insert(rec.end(), key_lem, key_lem + 768);
   uint8_t state[216];
   partial.save(state);
   rec.insert(rec.end(), state, state + 216);
   Blake2b h = partial;
-  for (int k = 0; k < 3; ++k) hash_g1(h, d.g1_s[k]), hash_g1(h, d.g1_sx[k]);
-  for (int k = 0; k < 3; ++k) hash_g2(h, g2_spx[k]);
+  h.update(key_u, 768);
   h.final(response_hash);
   rec.insert(rec.end(), 64, 0);  // nextChallenge: the caller's, once the uncompressed sections are hashed
   std::vector<uint8_t> prm;

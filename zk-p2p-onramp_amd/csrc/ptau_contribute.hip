@@ -41,15 +41,17 @@
 #include "prover.hpp"
 #include "ptau_contribute.hpp"
 #include "ptau_scale_kernels.hpp"
+#include "ptau_stream.hpp"
 #include "ptau_verify.hpp"
 #include "spans.hpp"
 #include "zkey_verify.hpp"
 
 namespace zkp {
 
-namespace {
-
 using pscale::Powers;
+using namespace pstream;
+
+namespace {
 
 // window bits of the ladder (gfft::scale): 2 measured 24 % (G1) and 44 % (G2) faster than 1 at power 20
 // (profiles/ptau_contribute.json); ZKP_PTAU_WINDOW=1|2 overrides the default
@@ -82,13 +84,17 @@ __global__ __launch_bounds__(TPB) void k_encode_points(const uint32_t* __restric
   pscale::encode_lem<F>(in, k.w, lem, u, c, i);
 }
 
-int window_bits() {
+}  // namespace
+
+int pstream::window_bits() {
   const char* e = std::getenv("ZKP_PTAU_WINDOW");
   if (!e || !*e) return DEFAULT_WINDOW;
   if ((e[0] != '1' && e[0] != '2') || e[1])
     throw ZkpError(ZKP_ERR_INVALID_ARG, std::string("ZKP_PTAU_WINDOW: 1 or 2 (got '") + e + "')");
   return e[0] - '0';
 }
+
+namespace {
 
 void launch_scale(bool g2, int wb, const uint32_t* in, size_t n, const Powers& pw, uint32_t* lem, uint32_t* u, uint32_t* c,
                   hipStream_t st) {
@@ -131,103 +137,59 @@ void words_of(const host::U256& v, uint32_t (&w)[8]) {
   for (int i = 0; i < 4; ++i) w[2 * i] = (uint32_t)v.w[i], w[2 * i + 1] = (uint32_t)(v.w[i] >> 32);
 }
 
-// Byte ranges handed from the pipeline to one hashing thread, in order.  The producer publishes chunk k and
-// may reuse its buffer once consumed() > k.
-class HashFeed {
- public:
-  void publish(const uint8_t* p, size_t len) {
+}  // namespace
+
+void HashFeed::publish(const uint8_t* p, size_t len) {
+  {
+    std::lock_guard<std::mutex> g(m_);
+    items_.push_back({p, len});
+  }
+  cv_.notify_all();
+}
+void HashFeed::close() {
+  {
+    std::lock_guard<std::mutex> g(m_);
+    closed_ = true;
+  }
+  cv_.notify_all();
+}
+void HashFeed::wait_consumed(size_t k) {
+  std::unique_lock<std::mutex> g(m_);
+  cv_.wait(g, [&] { return done_ > k || ended_; });
+}
+void HashFeed::end() {
+  {
+    std::lock_guard<std::mutex> g(m_);
+    ended_ = true;
+  }
+  cv_.notify_all();
+}
+void HashFeed::drain(Blake2b& h) {
+  for (;;) {
+    std::pair<const uint8_t*, size_t> it;
+    {
+      std::unique_lock<std::mutex> g(m_);
+      cv_.wait(g, [&] { return done_ < items_.size() || closed_; });
+      if (done_ == items_.size()) return;
+      it = items_[done_];
+    }
+    h.update(it.first, it.second);
     {
       std::lock_guard<std::mutex> g(m_);
-      items_.push_back({p, len});
+      ++done_;
     }
     cv_.notify_all();
   }
-  void close() {
-    {
-      std::lock_guard<std::mutex> g(m_);
-      closed_ = true;
-    }
-    cv_.notify_all();
-  }
-  void wait_consumed(size_t k) {  // until chunk k has been hashed (or the consumer has given up)
-    std::unique_lock<std::mutex> g(m_);
-    cv_.wait(g, [&] { return done_ > k || ended_; });
-  }
-  void end() {  // the consumer leaves: nobody waits for it any more
-    {
-      std::lock_guard<std::mutex> g(m_);
-      ended_ = true;
-    }
-    cv_.notify_all();
-  }
-  // the consumer: every published range into h, until close()
-  void drain(Blake2b& h) {
-    for (;;) {
-      std::pair<const uint8_t*, size_t> it;
-      {
-        std::unique_lock<std::mutex> g(m_);
-        cv_.wait(g, [&] { return done_ < items_.size() || closed_; });
-        if (done_ == items_.size()) return;
-        it = items_[done_];
-      }
-      h.update(it.first, it.second);
-      {
-        std::lock_guard<std::mutex> g(m_);
-        ++done_;
-      }
-      cv_.notify_all();
-    }
-  }
+}
 
- private:
-  std::mutex m_;
-  std::condition_variable cv_;
-  std::vector<std::pair<const uint8_t*, size_t>> items_;
-  size_t done_ = 0;
-  bool closed_ = false, ended_ = false;
-};
-
-// closes the feed and joins its thread on every way out
-struct HashThread {
-  HashFeed feed;
-  std::thread th;
-  ~HashThread() { finish(); }
-  void finish() {
-    feed.close();
-    if (th.joinable()) th.join();
-  }
-};
-
-struct Job {  // one section
-  int id;
-  bool g2;
-  size_t n;
-  const uint8_t* in;
-  uint8_t* out;
-  uint32_t first[8], ratio[8];
-};
-struct Chunk {
-  int job;
-  size_t start, m;
-};
-
-struct Slot {
-  DevBuf<> a, b, c;  // pass 1: input, zkey layout, compressed; pass 2: input, uncompressed, -
-  DevBuf<unsigned long long> dbad;
-  PinnedBuf<uint8_t> hlem, henc;
-  PinnedBuf<unsigned long long> hbad;
-  Event done;
-  Stream st;  // last: drained before the buffers go
-};
-
-std::vector<Chunk> chunks_of(const std::vector<Job>& jobs, size_t ch) {
+std::vector<Chunk> pstream::chunks_of(const std::vector<Job>& jobs, size_t ch) {
   std::vector<Chunk> v;
   for (size_t j = 0; j < jobs.size(); ++j)
     for (size_t at = 0; at < jobs[j].n; at += ch) v.push_back(Chunk{(int)j, at, std::min(ch, jobs[j].n - at)});
   return v;
 }
 
-void make_slots(Slot (&slot)[2], const std::vector<Job>& jobs, size_t ch, bool hashes) {
+void pstream::make_slots(Slot (&slot)[2], const std::vector<Job>& jobs, size_t ch, bool hashes) {
   size_t bytes = 0;
   for (const Job& j : jobs) bytes = std::max(bytes, std::min(ch, j.n) * (j.g2 ? 128 : 64));
   for (Slot& s : slot) {
@@ -241,10 +203,12 @@ void make_slots(Slot (&slot)[2], const std::vector<Job>& jobs, size_t ch, bool h
   }
 }
 
-// Pass 1 over the chunks: upload, point check, scale; the zkey-layout bytes into each job's out, the
-// compressed bytes (if feed) to the hashing thread.  bad_status: what an off-curve point is (with its message).
-void scale_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, int wb, HashFeed* feed,
-                zkp_status bad_status, const char* bad_prefix, Spans& sp, PtauContributeTimings& t) {
+// Pass 1 over the chunks (ptau_stream.hpp)
+void pstream::scale_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, int wb,
+                         HashFeed* feed, zkp_status bad_status, const char* bad_prefix, Spans& sp, PtauContributeTimings& t,
+                         double* decode_ms) {
+  bool enc = feed != nullptr;
+  for (const Job& j : jobs) enc = enc || j.out_enc;
   auto finish = [&](size_t k) {
     const auto t0 = std::chrono::steady_clock::now();
     Slot& s = slot[k % 2];
@@ -253,9 +217,10 @@ void scale_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector
     const size_t pb = j.g2 ? 128 : 64;
     HIPX(hipEventSynchronize(s.done));
     if (s.hbad[0])
-      throw ZkpError(bad_status, std::string(bad_prefix) + (feed ? "section " + std::to_string(j.id) + " " : "") + "point " +
+      throw ZkpError(bad_status, std::string(bad_prefix) + (j.id ? "section " + std::to_string(j.id) + " " : "") + "point " +
                                      std::to_string(s.hbad[1]) + " is not on the curve");
-    std::memcpy(j.out + c.start * pb, s.hlem.get(), c.m * pb);
+    if (j.out) std::memcpy(j.out + c.start * pb, s.hlem.get(), c.m * pb);
+    if (j.out_enc) std::memcpy(j.out_enc + c.start * pb / 2, s.henc.get(), c.m * pb / 2);
     if (feed) feed->publish(s.henc.get(), c.m * pb / 2);
     t.download_ms += wall_ms(t0);
   };
@@ -269,19 +234,24 @@ void scale_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector
     pscale::fill_powers(pw, j.first, j.ratio, c.start);
     {
       const auto t0 = std::chrono::steady_clock::now();
-      HIPX(hipMemcpyAsync(s.a, j.in + c.start * pb, c.m * pb, hipMemcpyHostToDevice, s.st));
+      HIPX(hipMemcpyAsync(decode_ms ? s.b : s.a, j.in + c.start * pb, c.m * pb, hipMemcpyHostToDevice, s.st));
       t.upload_ms += wall_ms(t0);
     }
     points_bad_reset(s.dbad, s.st);
+    if (decode_ms) {  // b is free until the scaling writes it: the staging buffer of the uncompressed bytes
+      sp.begin(s.st);
+      launch_decode(j.g2, s.b, c.m, c.start, s.a, s.dbad, s.st);
+      sp.end(s.st, decode_ms);
+    }
     sp.begin(s.st);
     points_check_resident(j.g2, s.a, c.m, c.start, s.dbad, s.st);
     sp.end(s.st, &t.parse_check_ms);
     sp.begin(s.st);
-    launch_scale(j.g2, wb, s.a, c.m, pw, s.b, nullptr, feed ? s.c.get() : nullptr, s.st);
+    launch_scale(j.g2, wb, s.a, c.m, pw, j.out ? s.b.get() : nullptr, nullptr, enc ? s.c.get() : nullptr, s.st);
     sp.end(s.st, j.g2 ? &t.g2_ms : &t.g1_ms);
     HIPX(hipMemcpyAsync(s.hbad.get(), s.dbad.get(), 16, hipMemcpyDeviceToHost, s.st));
-    HIPX(hipMemcpyAsync(s.hlem.get(), s.b.get(), c.m * pb, hipMemcpyDeviceToHost, s.st));
-    if (feed) HIPX(hipMemcpyAsync(s.henc.get(), s.c.get(), c.m * pb / 2, hipMemcpyDeviceToHost, s.st));
+    if (j.out) HIPX(hipMemcpyAsync(s.hlem.get(), s.b.get(), c.m * pb, hipMemcpyDeviceToHost, s.st));
+    if (enc) HIPX(hipMemcpyAsync(s.henc.get(), s.c.get(), c.m * pb / 2, hipMemcpyDeviceToHost, s.st));
     HIPX(hipEventRecord(s.done, s.st));
     ++t.chunks;
     if (k >= 1) finish(k - 1);
@@ -289,16 +259,20 @@ void scale_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector
   if (!chunks.empty()) finish(chunks.size() - 1);
 }
 
-// Pass 2: the new sections (each job's out) uncompressed, to the hashing thread
-void encode_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, HashFeed& feed,
-                 Spans& sp, PtauContributeTimings& t) {
+// Pass 2: the new sections uncompressed, to the hashing thread (ptau_stream.hpp)
+void pstream::encode_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, HashFeed& feed,
+                          Spans& sp, PtauContributeTimings& t, bool from_in) {
   ToZkey tz;
   pscale::fill_to_zkey(tz.w);
   auto finish = [&](size_t k) {
     const auto t0 = std::chrono::steady_clock::now();
     Slot& s = slot[k % 2];
+    const Chunk& c = chunks[k];
+    const Job& j = jobs[c.job];
+    const size_t pb = j.g2 ? 128 : 64;
     HIPX(hipEventSynchronize(s.done));
-    feed.publish(s.henc.get(), chunks[k].m * (jobs[chunks[k].job].g2 ? 128 : 64));
+    if (j.out_enc) std::memcpy(j.out_enc + c.start * pb, s.henc.get(), c.m * pb);
+    feed.publish(s.henc.get(), c.m * pb);
     t.download_ms += wall_ms(t0);
   };
   for (size_t k = 0; k < chunks.size(); ++k) {
@@ -309,7 +283,7 @@ void encode_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vecto
     if (k >= 2) feed.wait_consumed(k - 2);
     {
       const auto t0 = std::chrono::steady_clock::now();
-      HIPX(hipMemcpyAsync(s.a, j.out + c.start * pb, c.m * pb, hipMemcpyHostToDevice, s.st));
+      HIPX(hipMemcpyAsync(s.a, (from_in ? j.in : j.out) + c.start * pb, c.m * pb, hipMemcpyHostToDevice, s.st));
       t.upload_ms += wall_ms(t0);
     }
     sp.begin(s.st);
@@ -322,7 +296,35 @@ void encode_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vecto
   if (!chunks.empty()) finish(chunks.size() - 1);
 }
 
-}  // namespace
+void pstream::ptau_layout(const PtauFile& f, std::vector<uint8_t>& out, uint8_t* (&sec_out)[8]) {
+  size_t body = 12 + 12 + f.sec[1].len;
+  for (int id = 2; id <= 6; ++id) body += 12 + f.sec[id].len;
+  out.reserve(body + 12 + f.sec[7].len + 2048);  // section 7 with its new record is appended: no reallocation
+  out.resize(body);
+  uint8_t* o = out.data();
+  auto put32 = [&](uint32_t x) { std::memcpy(o, &x, 4), o += 4; };
+  auto put64 = [&](uint64_t x) { std::memcpy(o, &x, 8), o += 8; };
+  std::memcpy(o, "ptau", 4), o += 4;
+  put32(1), put32(7);
+  put32(1), put64(f.sec[1].len);
+  std::memcpy(o, f.sec[1].ptr, f.sec[1].len), o += f.sec[1].len;
+  for (int id = 2; id <= 6; ++id) {
+    put32((uint32_t)id), put64(f.sec[id].len);
+    sec_out[id] = o, o += f.sec[id].len;
+  }
+}
+
+// section 7: the count, the earlier records, the new one
+void pstream::ptau_append_section7(const PtauFile& f, std::vector<uint8_t>& out, const std::vector<uint8_t>& rec) {
+  const size_t old = f.sec[7].len - 4, s7 = 4 + old + rec.size();
+  uint32_t count;
+  std::memcpy(&count, f.sec[7].ptr, 4);
+  ++count;
+  const uint32_t id = 7;
+  const uint64_t l64 = s7;
+  auto app = [&](const void* p, size_t n) { out.insert(out.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
+  app(&id, 4), app(&l64, 8), app(&count, 4), app(f.sec[7].ptr + 4, old), app(rec.data(), rec.size());
+}
 
 PtauContributeTimings& ptau_contribute_timings() { return g_timings; }
 
@@ -344,7 +346,7 @@ void points_scale_powers(int device, bool g2, const uint8_t* points, size_t n, c
   const int wb = window_bits();
   if (!n) return;
   std::vector<Job> jobs(1);
-  jobs[0] = Job{0, g2, n, points, out, {}, {}};
+  jobs[0] = Job{0, g2, n, points, out, {}, {}, nullptr};
   reduced_words(first32, jobs[0].first);
   reduced_words(ratio32, jobs[0].ratio);
   HIPX(hipSetDevice(device));
@@ -376,32 +378,16 @@ std::vector<uint8_t> ptau_contribute(int device, const uint8_t* ptau, size_t len
   t.key_ms = wall_ms(t0);
   // ---- the output file: sections 1-6 laid out, 7 appended at the end
   const size_t N = f.N();
-  size_t body = 12 + 12 + f.sec[1].len;
-  for (int id = 2; id <= 6; ++id) body += 12 + f.sec[id].len;
   std::vector<uint8_t> out;
-  out.reserve(body + 12 + f.sec[7].len + 2048);  // section 7 with its new record is appended: no reallocation
-  out.resize(body);
   uint8_t* sec_out[8] = {};
-  {
-    uint8_t* o = out.data();
-    auto put32 = [&](uint32_t x) { std::memcpy(o, &x, 4), o += 4; };
-    auto put64 = [&](uint64_t x) { std::memcpy(o, &x, 8), o += 8; };
-    std::memcpy(o, "ptau", 4), o += 4;
-    put32(1), put32(7);
-    put32(1), put64(f.sec[1].len);
-    std::memcpy(o, f.sec[1].ptr, f.sec[1].len), o += f.sec[1].len;
-    for (int id = 2; id <= 6; ++id) {
-      put32((uint32_t)id), put64(f.sec[id].len);
-      sec_out[id] = o, o += f.sec[id].len;
-    }
-  }
+  ptau_layout(f, out, sec_out);
   std::vector<Job> jobs;
   {
     const uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
     uint32_t tau[8], alpha[8], beta[8];
     words_of(draw.prv[0], tau), words_of(draw.prv[1], alpha), words_of(draw.prv[2], beta);
     auto job = [&](int id, size_t n, const uint32_t (&first)[8], const uint32_t (&ratio)[8]) {
-      Job j{id, PtauFile::is_g2(id), n, f.sec[id].ptr, sec_out[id], {}, {}};
+      Job j{id, PtauFile::is_g2(id), n, f.sec[id].ptr, sec_out[id], {}, {}, nullptr};
       std::memcpy(j.first, first, 32), std::memcpy(j.ratio, ratio, 32);
       jobs.push_back(j);
     };
@@ -459,17 +445,7 @@ std::vector<uint8_t> ptau_contribute(int device, const uint8_t* ptau, size_t len
   }
   for (Slot& s : slot) HIPX(hipStreamSynchronize(s.st));
   sp.collect();
-  // ---- section 7: the count, the earlier records, the new one
-  {
-    const size_t old = f.sec[7].len - 4, s7 = 4 + old + rec.size();
-    uint32_t count;
-    std::memcpy(&count, f.sec[7].ptr, 4);
-    ++count;
-    const uint32_t id = 7;
-    const uint64_t l64 = s7;
-    auto app = [&](const void* p, size_t n) { out.insert(out.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
-    app(&id, 4), app(&l64, 8), app(&count, 4), app(f.sec[7].ptr + 4, old), app(rec.data(), rec.size());
-  }
+  ptau_append_section7(f, out, rec);
   t.total_ms = wall_ms(t_begin);
   g_timings = t;
   return out;

@@ -70,4 +70,18 @@ std::vector<uint8_t> ptau_record(const PtauDraw& d, const uint8_t challenge[64],
                                  const Blake2b& partial, uint32_t type, const char* name, const uint8_t* beacon,
                                  size_t beacon_len, uint32_t num_iterations_exp, uint8_t response_hash[64]);
 
+// The same record from the key's nine points themselves, in the zkey layout and uncompressed (768 bytes each,
+// the record's order: g1_s, g1_sx per secret, then the three g2_spx): what `import response` has, which never
+// sees the secrets.  ptau_record is this over ptau_key_forms.
+std::vector<uint8_t> ptau_record_of_key(const uint8_t key_lem[768], const uint8_t key_u[768], const uint8_t points_lem[448],
+                                        const Blake2b& partial, uint32_t type, const char* name, const uint8_t* beacon,
+                                        size_t beacon_len, uint32_t num_iterations_exp, uint8_t response_hash[64]);
+// The key of a draw against a challenge (its three G2 points are made here) in both forms
+void ptau_key_forms(const PtauDraw& d, const uint8_t challenge[64], uint8_t key_lem[768], uint8_t key_u[768]);
+// A key as a response file holds it -> the zkey layout.  Every point canonical (coordinates below p; infinity
+// as 0x40 then zeros) and on its curve, else ZKP_ERR_FORMAT "response: key point <k> ..." (k: 0-5 G1, 6-8 G2)
+void ptau_key_from_uncompressed(const uint8_t key_u[768], uint8_t key_lem[768]);
+// ptau_last_challenge and the last record's response hash with it (false: no contribution, nothing written)
+bool ptau_last_hashes(const uint8_t* sec7, size_t len, uint8_t challenge[64], uint8_t response[64]);
+
 }  // namespace zkp

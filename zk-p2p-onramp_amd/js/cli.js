@@ -23,7 +23,10 @@
  *   node cli.js powersoftau new bn128 <power> <out.ptau> [-v]
  *   node cli.js powersoftau contribute <in.ptau> <out.ptau> [--name=|-n=name] [-e=entropy] [-v]
  *   node cli.js powersoftau beacon <in.ptau> <out.ptau> <beaconHashHex> <numIterationsExp> [-n=name] [-v]
- * (`export challenge`, `challenge contribute` and `import response`, script lines 12-14, are not implemented)
+ * and the path of a contributor who never holds the ptau (reference circuit/scripts/generate_keys_phase1.sh:12-14):
+ *   node cli.js powersoftau export challenge <in.ptau> <challenge> [-v]
+ *   node cli.js powersoftau challenge contribute bn128 <challenge> <response> [-e=entropy] [-v]
+ *   node cli.js powersoftau import response <old.ptau> <response> <new.ptau> [-n=|--name=name] [-v]
  */
 const fs = require('fs');
 const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, powersOfTau, release } = require('./groth16');
@@ -38,7 +41,10 @@ const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.
               '       cli.js powersoftau verify <pot.ptau> [-v]\n' +
               '       cli.js powersoftau new bn128 <power> <out.ptau> [-v]\n' +
               '       cli.js powersoftau contribute <in.ptau> <out.ptau> [--name=|-n=name] [-e=entropy] [-v]\n' +
-              '       cli.js powersoftau beacon <in.ptau> <out.ptau> <beaconHashHex> <numIterationsExp> [-n=name] [-v]\n';
+              '       cli.js powersoftau beacon <in.ptau> <out.ptau> <beaconHashHex> <numIterationsExp> [-n=name] [-v]\n' +
+              '       cli.js powersoftau export challenge <in.ptau> <challenge> [-v]\n' +
+              '       cli.js powersoftau challenge contribute bn128 <challenge> <response> [-e=entropy] [-v]\n' +
+              '       cli.js powersoftau import response <old.ptau> <response> <new.ptau> [-n=|--name=name] [-v]\n';
 
 async function main(argv) {
   if (argv.length === 5 && argv[0] === 'zkey' && argv[1] === 'export' && argv[2] === 'soliditycalldata') {
@@ -65,6 +71,35 @@ async function main(argv) {
       error: (m) => process.stdout.write(`[ERROR] snarkJS: ${m}\n`),
     };
     return (await powersOfTau.verify(named[2], logger)) ? 0 : 1;
+  }
+  if (argv[0] === 'powersoftau' && ['export', 'challenge', 'import'].includes(argv[1])) {
+    const verbose = argv.includes('-v') || argv.includes('--verbose');
+    const logger = verbose ? { info: (m) => process.stdout.write(`[INFO]  snarkJS: ${m}\n`) } : undefined;
+    const pos = argv.filter((a) => !/^(-n|--name|-e|--entropy)=/.test(a) && a !== '-v' && a !== '--verbose');
+    const opt = (re) => {
+      const a = argv.find((x) => re.test(x));
+      return a === undefined ? undefined : a.replace(/^[^=]*=/, '');
+    };
+    if (argv[1] === 'export' && pos[2] === 'challenge' && pos.length === 5) {
+      await powersOfTau.exportChallenge(pos[3], pos[4], logger);
+      return 0;
+    }
+    if (argv[1] === 'challenge' && pos[2] === 'contribute' && pos.length === 6) {
+      try {
+        await powersOfTau.challengeContribute(pos[3], pos[4], pos[5], opt(/^(-e|--entropy)=/), logger);
+      } catch (e) {  // an unknown curve: snarkjs' error line, exit 1
+        if (!/^Curve not supported/.test(e.message)) throw e;
+        process.stdout.write(`[ERROR] snarkJS: Error: ${e.message}\n`);
+        return 1;
+      }
+      return 0;
+    }
+    if (argv[1] === 'import' && pos[2] === 'response' && pos.length === 6) {
+      await powersOfTau.importResponse(pos[3], pos[4], pos[5], opt(/^(-n|--name)=/), true, logger);
+      return 0;
+    }
+    process.stderr.write(USAGE);
+    return 1;
   }
   if (argv[0] === 'powersoftau' && ['new', 'contribute', 'beacon'].includes(argv[1])) {
     const verbose = argv.includes('-v') || argv.includes('--verbose');

@@ -334,6 +334,58 @@ async function beaconPtau(oldPtauName, newPtauName, name, beaconHashStr, numIter
   return out;
 }
 
+function writeOutput(target, out) {
+  if (typeof target === 'string') fs.writeFileSync(target, out);
+  else if (target && typeof target === 'object' && target.type === 'mem') target.data = out;
+}
+
+function requireBn128(curve) {
+  const name = String(curve && curve.name ? curve.name : curve);
+  if (!['BN128', 'BN254', 'ALTBN128'].includes(name.toUpperCase().replace(/[^0-9A-Z]/g, ''))) {
+    throw new Error(`Curve not supported: ${name}`);
+  }
+}
+
+/*
+ * snarkjs' `powersOfTau.exportChallenge(pTauFilename, challengeFilename, logger)` (the `powersoftau export
+ * challenge` step, reference circuit/scripts/generate_keys_phase1.sh:12): the last response hash and sections
+ * 2-6 uncompressed, encoded on the GPU.  A file whose sections do not hash to its last challenge throws.
+ */
+async function exportChallenge(ptauName, challengeName, logger, device) {
+  const out = addon.ptauExportChallenge(readInput(ptauName), device || 0);
+  writeOutput(challengeName, out);
+  if (logger && logger.info) logger.info(`powersoftau export challenge: ${out.length} bytes`);
+  return out;
+}
+
+/*
+ * snarkjs' `powersOfTau.challengeContribute(curve, challengeFilename, responseFileName, entropy, logger)` (the
+ * `powersoftau challenge contribute bn128` step, reference circuit/scripts/generate_keys_phase1.sh:13): one
+ * contribution to a challenge file on the GPU, by a party that never holds the ptau.  Only bn128 exists here.
+ */
+async function challengeContribute(curve, challengeName, responseName, entropy, logger, device) {
+  requireBn128(curve);
+  const out = addon.ptauChallengeContribute(readInput(challengeName), entropy == null ? '' : String(entropy), device || 0);
+  writeOutput(responseName, out);
+  if (logger && logger.info) logger.info(`powersoftau challenge contribute: ${out.length} bytes`);
+  return out;
+}
+
+/*
+ * snarkjs' `powersOfTau.importResponse(oldPtauFilename, contributionFilename, newPTauFilename, name, importPoints,
+ * logger)` (the `powersoftau import response` step, reference circuit/scripts/generate_keys_phase1.sh:14): the
+ * response's points decompressed on the GPU, a record appended to section 7.  The points are always imported
+ * (snarkjs' --nopoints is not offered); the contribution itself is checked by powersOfTau.verify on the result.
+ */
+async function importResponse(oldPtauName, responseName, newPtauName, name, importPoints, logger, device) {
+  if (importPoints === false) throw new Error('importResponse: importing without the points is not supported');
+  const out = addon.ptauImportResponse(readInput(oldPtauName), readInput(responseName), name ? String(name) : undefined,
+                                       device || 0);
+  writeOutput(newPtauName, out);
+  if (logger && logger.info) logger.info(`powersoftau import response ${name || ''}: ${out.length} bytes`);
+  return out;
+}
+
 function release() {
   for (const h of provers.values()) addon.freeProver(h);
   for (const h of memProvers.values()) addon.freeProver(h);
@@ -345,7 +397,8 @@ module.exports = {
   groth16: { prove, proveBatch },
   proveBatch,
   zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit },
-  powersOfTau: { newAccumulator, contribute: contributePtau, beacon: beaconPtau, preparePhase2, verify: verifyPtau },
+  powersOfTau: { newAccumulator, contribute: contributePtau, beacon: beaconPtau, preparePhase2, verify: verifyPtau,
+                 exportChallenge, challengeContribute, importResponse },
   preparePhase2,
   verifyFromR1cs,
   verifyFromInit,

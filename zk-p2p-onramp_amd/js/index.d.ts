@@ -56,6 +56,20 @@ export declare const powersOfTau: {
   /** `snarkjs powersoftau verify` (zkp_ptau_verify): the contribution chain on the host, every point section
    *  on the GPU; resolves to the verdict, the failing check goes to logger.error */
   verify(ptauName: Input, logger?: VerifyLogger, device?: number): Promise<boolean>;
+  /** `snarkjs powersoftau export challenge` on the GPU (zkp_ptau_export_challenge): the challenge file a third
+   *  party contributes to; throws when the sections do not hash to the file's last challenge */
+  exportChallenge(ptauName: Input, challengeName?: string | { type: "mem"; data?: Uint8Array }, logger?: Logger,
+    device?: number): Promise<Uint8Array>;
+  /** `snarkjs powersoftau challenge contribute bn128` on the GPU (zkp_ptau_challenge_contribute): the response
+   *  file; any curve but bn128 throws */
+  challengeContribute(curve: string | { name: string }, challengeName: Input,
+    responseName?: string | { type: "mem"; data?: Uint8Array }, entropy?: string, logger?: Logger, device?: number):
+    Promise<Uint8Array>;
+  /** `snarkjs powersoftau import response` on the GPU (zkp_ptau_import_response): the response's points
+   *  decompressed and a record appended; importPoints === false is not supported.  The contribution is checked
+   *  by verify on the result, not here */
+  importResponse(oldPtauName: Input, responseName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array },
+    name?: string, importPoints?: boolean, logger?: Logger, device?: number): Promise<Uint8Array>;
 };
 export declare function preparePhase2(oldPtauName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array },
                                       logger?: Logger, device?: number): Promise<Buffer>;

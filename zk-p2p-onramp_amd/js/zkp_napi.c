@@ -18,6 +18,9 @@
  *   ptauNew(power, ceremonyPower?)             -> Buffer (`snarkjs powersoftau new bn128`, host only)
  *   ptauContribute(ptauBuffer, entropy, name?, device?) -> Buffer (`snarkjs powersoftau contribute`, synchronous)
  *   ptauBeacon(ptauBuffer, beaconBuffer, numIterationsExp, device?, name?) -> Buffer (`snarkjs powersoftau beacon`)
+ *   ptauExportChallenge(ptauBuffer, device?)   -> Buffer (`snarkjs powersoftau export challenge`)
+ *   ptauChallengeContribute(challengeBuffer, entropy, device?, rand64?) -> Buffer (`powersoftau challenge contribute`)
+ *   ptauImportResponse(ptauBuffer, responseBuffer, name?, device?) -> Buffer (`snarkjs powersoftau import response`)
  *   zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify`)
  *   version()
  * prove()/proveBatch() run on the libuv threadpool (napi_async_work), so the JS main
@@ -369,6 +372,97 @@ static napi_value js_ptau_beacon(napi_env env, napi_callback_info info) {
   const char* nm = argc > 4 ? opt_string(env, argv[4], name, sizeof name) : NULL;
   zkp_status st = zkp_ptau_beacon(device, (const uint8_t*)ptau, ptau_len, (const uint8_t*)beacon, beacon_len, e, nm,
                                   &out, &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return buffer_out(env, out, out_len);
+}
+
+/* ptauExportChallenge(ptauBuffer, device?) -> Buffer: `snarkjs powersoftau export challenge`
+ * (zkp_ptau_export_challenge), synchronous -- a setup step */
+static napi_value js_ptau_export_challenge(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &b0);
+  if (!b0) {
+    napi_throw_type_error(env, NULL, "ptauExportChallenge(ptauBuffer, device?)");
+    return NULL;
+  }
+  int device = 0;
+  if (argc > 1) napi_get_value_int32(env, argv[1], &device);
+  void* ptau;
+  size_t ptau_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &ptau, &ptau_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  zkp_status st = zkp_ptau_export_challenge(device, (const uint8_t*)ptau, ptau_len, &out, &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return buffer_out(env, out, out_len);
+}
+
+/* ptauChallengeContribute(challengeBuffer, entropyString, device?, rand64Buffer?) -> Buffer: `snarkjs powersoftau
+ * challenge contribute bn128` (zkp_ptau_challenge_contribute; rand64: the 64 random bytes mixed with the entropy,
+ * default the OS CSPRNG), synchronous */
+static napi_value js_ptau_challenge_contribute(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false, b3 = false;
+  char ent[4096];
+  const char* e = NULL;
+  if (argc >= 2) {
+    napi_is_buffer(env, argv[0], &b0);
+    e = opt_string(env, argv[1], ent, sizeof ent);
+  }
+  void* rand64 = NULL;
+  size_t rand_len = 0;
+  if (argc > 3) {
+    napi_is_buffer(env, argv[3], &b3);
+    if (b3) NAPI_CALL(env, napi_get_buffer_info(env, argv[3], &rand64, &rand_len));
+  }
+  if (!b0 || !e || (b3 && rand_len != 64)) {
+    napi_throw_type_error(env, NULL, "ptauChallengeContribute(challengeBuffer, entropyString, device?, rand64Buffer?)");
+    return NULL;
+  }
+  int device = 0;
+  if (argc > 2) napi_get_value_int32(env, argv[2], &device);
+  void* ch;
+  size_t ch_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &ch, &ch_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  zkp_status st = zkp_ptau_challenge_contribute(device, (const uint8_t*)ch, ch_len, (const uint8_t*)rand64, e, &out, &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return buffer_out(env, out, out_len);
+}
+
+/* ptauImportResponse(ptauBuffer, responseBuffer, nameString?, device?) -> Buffer: `snarkjs powersoftau import
+ * response` (zkp_ptau_import_response), synchronous */
+static napi_value js_ptau_import_response(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false, b1 = false;
+  if (argc >= 2) {
+    napi_is_buffer(env, argv[0], &b0);
+    napi_is_buffer(env, argv[1], &b1);
+  }
+  if (!b0 || !b1) {
+    napi_throw_type_error(env, NULL, "ptauImportResponse(ptauBuffer, responseBuffer, nameString?, device?)");
+    return NULL;
+  }
+  char name[256];
+  const char* nm = argc > 2 ? opt_string(env, argv[2], name, sizeof name) : NULL;
+  int device = 0;
+  if (argc > 3) napi_get_value_int32(env, argv[3], &device);
+  void *ptau, *resp;
+  size_t ptau_len, resp_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &ptau, &ptau_len));
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &resp, &resp_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  zkp_status st = zkp_ptau_import_response(device, (const uint8_t*)ptau, ptau_len, (const uint8_t*)resp, resp_len, nm, &out,
+                                           &out_len);
   if (st != ZKP_OK) return throw_status(env, st);
   return buffer_out(env, out, out_len);
 }
@@ -771,6 +865,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauNew", NULL, js_ptau_new, NULL, NULL, NULL, napi_default, NULL},
       {"ptauContribute", NULL, js_ptau_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"ptauBeacon", NULL, js_ptau_beacon, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauExportChallenge", NULL, js_ptau_export_challenge, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauChallengeContribute", NULL, js_ptau_challenge_contribute, NULL, NULL, NULL, napi_default, NULL},
+      {"ptauImportResponse", NULL, js_ptau_import_response, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromR1cs", NULL, js_zkey_verify_r1cs, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);

@@ -180,6 +180,21 @@ def load_library(path: str = LIB_PATH):
             for name in ("zkp_ptau_new", "zkp_ptau_contribute", "zkp_ptau_beacon", "zkp_ptau_contribute_timings",
                          "zkp_points_scale_powers"):
                 getattr(lib, name).restype = ctypes.c_int
+        if hasattr(lib, "zkp_ptau_import_response"):  # powersoftau export challenge / challenge contribute / import response
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            lib.zkp_ptau_export_challenge.argtypes = [ctypes.c_int, u8p, sz, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+            lib.zkp_ptau_challenge_contribute.argtypes = [ctypes.c_int, u8p, sz, u8p, ctypes.c_char_p, ctypes.POINTER(u8p),
+                                                          ctypes.POINTER(sz)]
+            lib.zkp_ptau_import_response.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, ctypes.c_char_p, ctypes.POINTER(u8p),
+                                                     ctypes.POINTER(sz)]
+            lib.zkp_ptau_challenge_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+            lib.zkp_points_decompress.argtypes = [ctypes.c_int, ctypes.c_int, u8p, sz, u8p, u64p, u64p]
+            lib.zkp_points_from_uncompressed.argtypes = [ctypes.c_int, ctypes.c_int, u8p, sz, u8p, u64p, u64p]
+            lib.zkp_field_sqrt.argtypes = [ctypes.c_int, ctypes.c_int, u8p, sz, u8p, u8p]
+            for name in ("zkp_ptau_export_challenge", "zkp_ptau_challenge_contribute", "zkp_ptau_import_response",
+                         "zkp_ptau_challenge_timings", "zkp_points_decompress", "zkp_points_from_uncompressed",
+                         "zkp_field_sqrt"):
+                getattr(lib, name).restype = ctypes.c_int
         for name in ("zkp_zkey_verify_frominit", "zkp_zkey_verify", "zkp_zkey_verify_timings", "zkp_rlc_coeffs",
                      "zkp_points_check", "zkp_rlc_g1", "zkp_ptau_verify", "zkp_ptau_verify_sections", "zkp_ptau_verify_timings",
                      "zkp_g2_subgroup_check", "zkp_rlc_pairs"):
@@ -897,6 +912,97 @@ def points_scale_powers(points_lem: bytes, first: int, ratio: int, g2: bool = Fa
     _check(load_library().zkp_points_scale_powers(device, 1 if g2 else 0, pp, len(points_lem) // pb, fp, rp,
                                                   ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8))))
     return bytes(out)[:len(points_lem)]
+
+
+def ptau_export_challenge(ptau: bytes, device: int = 0) -> bytes:
+    """`snarkjs powersoftau export challenge <in.ptau> <challenge>` (zkp_ptau_export_challenge): the last response
+    hash and sections 2-6 uncompressed, 384 * 2^power + 128 bytes.  Its Blake2b-512 is the challenge; a file whose
+    sections do not hash to the challenge its section 7 implies raises ZkpError."""
+    lib = load_library()
+    pp, plen, pk = _in(ptau)
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_ptau_export_challenge(device, pp, plen, ctypes.byref(out), ctypes.byref(n)))
+    return _take(lib, out, n)
+
+
+def ptau_challenge_contribute(challenge: bytes, entropy: str, rand64: bytes = None, device: int = 0) -> bytes:
+    """`snarkjs powersoftau challenge contribute bn128 <challenge> <response> -e=<entropy>`
+    (zkp_ptau_challenge_contribute): one contribution to a challenge file on the GPU -> the response file (the
+    challenge hash, the new sections compressed, the key), 192 * 2^power + 864 bytes.  rand64 as ptau_contribute."""
+    lib = load_library()
+    cp, clen, ck = _in(challenge)
+    rp = None
+    if rand64 is not None:
+        if len(rand64) != 64:
+            raise ValueError("rand64 must be 64 bytes")
+        rp, rk = _buf(bytes(rand64))
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_ptau_challenge_contribute(device, cp, clen, rp, entropy.encode(), ctypes.byref(out), ctypes.byref(n)))
+    return _take(lib, out, n)
+
+
+def ptau_import_response(ptau: bytes, response: bytes, name=None, device: int = 0) -> bytes:
+    """`snarkjs powersoftau import response <old.ptau> <response> <new.ptau> [-n=]` (zkp_ptau_import_response):
+    the response's points decompressed on the GPU, a type-0 record appended.  The contribution itself is checked
+    by ptau_verify on the result, not here."""
+    lib = load_library()
+    pp, plen, pk = _in(ptau)
+    rp, rlen, rk = _in(response)
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_ptau_import_response(device, pp, plen, rp, rlen, None if name is None else name.encode(),
+                                        ctypes.byref(out), ctypes.byref(n)))
+    return _take(lib, out, n)
+
+
+def ptau_challenge_timings() -> dict:
+    """ms of the calling thread's last export / challenge contribute / import (zkp_ptau_challenge_timings)."""
+    out = (ctypes.c_double * 14)()
+    _check(load_library().zkp_ptau_challenge_timings(out, 14))
+    keys = ["total", "parse_point_check", "challenge_hash", "key", "upload", "decode", "g1_decompress", "g2_decompress",
+            "g1_scale", "g2_scale", "encode", "download", "hash_threads", "chunks"]
+    return dict(zip(keys, list(out)))
+
+
+def _points_to_lem(fn, data: bytes, in_pb: int, out_pb: int, device: int):
+    if len(data) % in_pb:
+        raise ValueError("points of %d bytes each" % in_pb)
+    n = len(data) // in_pb
+    pp, pk = _buf(bytes(data) or b"\0")
+    out = (ctypes.c_uint8 * max(1, n * out_pb))()
+    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(fn(device, 1 if out_pb == 128 else 0, pp, n, ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(bad),
+              ctypes.byref(first)))
+    return bytes(out)[:n * out_pb], bad.value, (first.value if bad.value else None)
+
+
+def points_decompress(compressed: bytes, g2: bool = False, device: int = 0):
+    """Kernel-level (zkp_points_decompress): compressed points -> (zkey-layout bytes, bad, first_bad); a refused
+    point (flag misuse, x >= p, x^3 + b a non-residue) is written as zeros."""
+    return _points_to_lem(load_library().zkp_points_decompress, compressed, 64 if g2 else 32, 128 if g2 else 64, device)
+
+
+def points_from_uncompressed(data: bytes, g2: bool = False, device: int = 0):
+    """Kernel-level (zkp_points_from_uncompressed): uncompressed points -> (zkey-layout bytes, bad, first_bad);
+    refused: a coordinate >= p, 0x40 with anything but zeros beside it.  The curve equation is points_check's."""
+    return _points_to_lem(load_library().zkp_points_from_uncompressed, data, 128 if g2 else 64, 128 if g2 else 64, device)
+
+
+def field_sqrt(elements: bytes, fq2: bool = False, device: int = 0):
+    """Kernel-level (zkp_field_sqrt): elements of Fq (32 bytes LE) or Fq2 (c0 then c1) -> (roots in the same form
+    or zeros, is_square bytes)."""
+    eb = 64 if fq2 else 32
+    if len(elements) % eb:
+        raise ValueError("elements of %d bytes each" % eb)
+    n = len(elements) // eb
+    pp, pk = _buf(bytes(elements) or b"\0")
+    out = (ctypes.c_uint8 * max(1, n * eb))()
+    sq = (ctypes.c_uint8 * max(1, n))()
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    _check(load_library().zkp_field_sqrt(device, 1 if fq2 else 0, pp, n, ctypes.cast(out, u8p), ctypes.cast(sq, u8p)))
+    return bytes(out)[:n * eb], bytes(sq)[:n]
 
 
 def g2_subgroup_check(points_lem: bytes, device: int = 0):
