@@ -167,7 +167,12 @@ def test_field_sqrt(fq2):
 
 # ------------------------------------------------------------------ refusals that need the device
 
-def test_challenge_with_an_off_curve_point_names_it():
+@pytest.mark.parametrize("chunk", [None, "4"], ids=["default", "chunk4"])
+def test_challenge_with_an_off_curve_point_names_it(monkeypatch, chunk):
+    """chunk 4: section 3 point 5 is local index 1 of that section's second chunk, on the odd slot, and the other
+    slot is busy when the refusal is thrown"""
+    if chunk:
+        monkeypatch.setenv("ZKP_PTAU_CHUNK", chunk)
     challenge = bytearray(_model_chain(3, 1)[0])
     n = 8
     at = 64 + 64 * (2 * n - 1) + 128 * 5  # section 3, point 5
@@ -185,7 +190,12 @@ def test_challenge_with_an_off_curve_point_names_it():
     assert (e.value.status, e.value.message) == (3, "challenge: section 3 point 5 is not on the curve")
 
 
-def test_response_with_a_non_residue_x_names_it():
+@pytest.mark.parametrize("chunk", [None, "4"], ids=["default", "chunk4"])
+def test_response_with_a_non_residue_x_names_it(monkeypatch, chunk):
+    """chunk 4: section 4 point 6 is in that section's second chunk; the other slot is busy and the hashing thread
+    live when the refusal is thrown"""
+    if chunk:
+        monkeypatch.setenv("ZKP_PTAU_CHUNK", chunk)
     f = _stage(3, 1)
     response = bytearray(_model_chain(3, 1)[1])
     n = 8

@@ -208,7 +208,12 @@ def test_lagrange_sections_are_dropped():
     assert got == pm.contribute(_model_stage(2, 1), mpc.entropy_rng(RAND64_B, "second"), None)
 
 
-def test_off_curve_point_names_its_section_and_index():
+@pytest.mark.parametrize("chunk", [None, "4"], ids=["default", "chunk4"])
+def test_off_curve_point_names_its_section_and_index(monkeypatch, chunk):
+    """chunk 4: section 2 is four chunks and section 3 point 5 is local index 1 of that section's second chunk, on
+    the odd slot; the refusal is thrown with a chunk in flight on the other slot and the hashing thread live"""
+    if chunk:
+        monkeypatch.setenv("ZKP_PTAU_CHUNK", chunk)
     secs = _sections(_model_stage(3, 1))
     x = bytearray(secs[3])
     x[5 * 128 + 64] ^= 1  # y.c0 of point 5

@@ -264,12 +264,10 @@ namespace {
 // snarkjs misc.getRandomRng seeded as `contribute -e=<entropy>` seeds it: Blake2b(64 random bytes || entropy)
 zkp::ChaChaRng entropy_rng(const uint8_t* rand64, const char* entropy) {
   uint8_t rnd[64];
-  if (rand64) {
+  if (rand64)
     std::memcpy(rnd, rand64, 64);
-  } else {  // 64 bytes from the OS CSPRNG
-    std::ifstream f("/dev/urandom", std::ios::binary);
-    if (!f.read(reinterpret_cast<char*>(rnd), 64)) throw zkp::ZkpError(ZKP_ERR_IO, "cannot read /dev/urandom");
-  }
+  else
+    zkp::os_random(rnd, 64);
   zkp::Blake2b hh;
   hh.update(rnd, 64);
   hh.update(entropy, std::strlen(entropy));

@@ -12,6 +12,7 @@
 #include "prover.hpp"
 #include "ptau_contribute.hpp"
 #include "ptau_verify.hpp"
+#include "spans.hpp"
 #include "zkey_verify.hpp"
 
 namespace zkp {
@@ -680,11 +681,13 @@ BeaconParams parse_contribution_params(const std::vector<uint8_t>& prm) {
   return b;
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
+
+void os_random(uint8_t* out, size_t n) {
+  const std::string dev = "/dev/urandom";
+  std::ifstream f(dev, std::ios::binary);
+  if (!f.read(reinterpret_cast<char*>(out), (std::streamsize)n)) throw ZkpError(ZKP_ERR_IO, "cannot read " + dev);
+}
 
 bool zkey_verify_frominit(int device, const uint8_t* init, size_t init_len, const uint8_t* key, size_t key_len,
                           const uint8_t* seed32, std::string& msg, VerifyTimings* timings) {
@@ -692,7 +695,7 @@ bool zkey_verify_frominit(int device, const uint8_t* init, size_t init_len, cons
   VerifyTimings tm;
   auto verdict = [&](bool ok, const std::string& m) {
     msg = m;
-    tm.total_ms = ms_since(t_begin);
+    tm.total_ms = wall_ms(t_begin);
     if (timings) *timings = tm;
     return ok;
   };
@@ -776,21 +779,19 @@ bool zkey_verify_frominit(int device, const uint8_t* init, size_t init_len, cons
   if (!same_ratio(g1gen, cur, g2gen, h.delta2)) return bad("INVALID: delta2");
   // 5. csHash
   if (std::memcmp(mpc.cs_hash, mpc0.cs_hash, 64) != 0) return bad("INVALID: circuit does not match (csHash)");
-  tm.host_ms = ms_since(t_begin);
+  tm.host_ms = wall_ms(t_begin);
   // 6. the sections no contribution touches
   const auto t_cmp = std::chrono::steady_clock::now();
   for (int id : {3, 4, 5, 6, 7})
     if (s[id].len != s0[id].len || (s[id].len && std::memcmp(s[id].ptr, s0[id].ptr, s[id].len) != 0))
       return bad("INVALID: section " + std::to_string(id) + " is not identical to the initial key's");
-  tm.compare_ms = ms_since(t_cmp);
+  tm.compare_ms = wall_ms(t_cmp);
   // 7. L, then H: new = old * delta_init / delta
   uint8_t seed[32];
-  if (seed32) {
+  if (seed32)
     std::memcpy(seed, seed32, 32);
-  } else {
-    std::ifstream f("/dev/urandom", std::ios::binary);
-    if (!f.read(reinterpret_cast<char*>(seed), 32)) throw ZkpError(ZKP_ERR_IO, "cannot read /dev/urandom");
-  }
+  else
+    os_random(seed, 32);
   uint64_t first_index = 0;
   for (int id : {8, 9}) {
     const std::string name = id == 8 ? "L" : "H";
@@ -1017,14 +1018,14 @@ bool ptau_verify(int device, const uint8_t* ptau, size_t len, const uint8_t* see
     msg = m;
     PtauVerifyTimings& t = ptau_verify_timings();
     t.contributions_ms = contrib_ms, t.first_challenge_ms = first_ms, t.next_challenge_ms = next_ms;
-    t.total_ms = ms_since(t_begin);
+    t.total_ms = wall_ms(t_begin);
     return ok;
   };
   if (cs.empty()) return verdict(false, "This file has no contribution! It cannot be used in production");
   first_thread = std::thread([&] {
     const auto t0 = std::chrono::steady_clock::now();
     first_challenge(f.ceremony_power, first);
-    first_ms = ms_since(t0);
+    first_ms = wall_ms(t0);
   });
   const Affine<HFq> g1gen{fq_small(1), fq_small(2), false};
   const Affine<HFq2> g2gen = g2_generator();
@@ -1039,7 +1040,7 @@ bool ptau_verify(int device, const uint8_t* ptau, size_t len, const uint8_t* see
       prev = PtauPrev{p.tau_g1, p.alpha_g1, p.beta_g1, p.tau_g2, p.beta_g2, p.next_challenge};
     }
     const std::string m = check_ptau_contribution(i, cs[i], prev);
-    contrib_ms += ms_since(t0);
+    contrib_ms += wall_ms(t0);
     return m;
   };
   // the last contribution, its ties to the sections, the sections, the next challenge, then the earlier
@@ -1069,7 +1070,7 @@ bool ptau_verify(int device, const uint8_t* ptau, size_t len, const uint8_t* see
     hash_points<128>(h, f.sec[6].ptr, 1);
     uint8_t d[64];
     h.final(d);
-    next_ms = ms_since(t0);
+    next_ms = wall_ms(t0);
     if (std::memcmp(d, last.next_challenge, 64) != 0)
       return verdict(false, "Hash of the values does not match the next challenge of the last contributor in the contributions section");
   }

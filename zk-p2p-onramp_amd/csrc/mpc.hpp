@@ -48,6 +48,8 @@ struct ChaChaRng {
 };
 // the seed of a 32+-byte hash: its first 8 big-endian 32-bit words
 void seed_from_hash(const uint8_t* h, uint32_t seed[8]);
+// n bytes from the OS CSPRNG, or ZKP_ERR_IO naming the device that could not be read
+void os_random(uint8_t* out, size_t n);
 
 struct MpcContribution {
   host::Affine<host::Fq> delta_after, g1_s, g1_sx;

@@ -13,6 +13,9 @@
 //                       uncompressed for the next-challenge hash), download both.  One pass: the response
 //                       hash, with which the next-challenge hash begins, is the hash of the response file
 //                       itself, which the hashing thread computes from the input before it takes the chunks.
+//
+// The passes, the slots and the kernels of the three are ptau_stream.hip; this unit holds the commands and the
+// kernel-level entries of ptau_challenge.hpp.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -30,44 +33,12 @@
 #include "ptau_stream.hpp"
 #include "ptau_verify.hpp"
 #include "spans.hpp"
-#include "zkey_verify.hpp"
 
 namespace zkp {
 
 using namespace pstream;
 
 namespace {
-
-constexpr int TPB = 128;
-unsigned grid(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-
-struct alignas(16) ToZkey {
-  uint32_t w[8];
-};
-
-__device__ __forceinline__ void count_bad(unsigned long long* bad, uint64_t index) {
-  atomicAdd(&bad[0], 1ull);
-  atomicMin(&bad[1], (unsigned long long)index);
-}
-
-// One thread per uncompressed point: its zkey layout (zeros and counted if refused)
-template <class F>
-__global__ __launch_bounds__(TPB) void k_decode_points(const uint32_t* __restrict__ in, size_t n, uint64_t base, ToZkey k,
-                                                       uint32_t* __restrict__ lem, unsigned long long* __restrict__ bad) {
-  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  if (pdec::decode_lane<F>(in, k.w, lem, i)) count_bad(bad, base + i);
-}
-
-// One thread per compressed point: y by a square root, then the streams that are asked for
-template <class F>
-__global__ __launch_bounds__(TPB) void k_decompress_points(const uint32_t* __restrict__ in, size_t n, uint64_t base,
-                                                           pdec::Consts k, uint32_t* __restrict__ lem,
-                                                           uint32_t* __restrict__ u, unsigned long long* __restrict__ bad) {
-  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  if (pdec::decompress_lane<F>(in, k, lem, u, i)) count_bad(bad, base + i);
-}
 
 template <class F>
 __global__ __launch_bounds__(TPB) void k_field_sqrt(const uint32_t* __restrict__ in, size_t n, pdec::Consts k,
@@ -77,73 +48,10 @@ __global__ __launch_bounds__(TPB) void k_field_sqrt(const uint32_t* __restrict__
   pdec::sqrt_lane<F>(in, k, out, is_square, i);
 }
 
-void launch_decompress(bool g2, const uint32_t* in, size_t n, uint64_t base, const pdec::Consts& k, uint32_t* lem,
-                       uint32_t* u, unsigned long long* bad, hipStream_t st) {
-  if (!n) return;
-  if (g2)
-    hipLaunchKernelGGL(k_decompress_points<Fq2>, dim3(grid(n)), dim3(TPB), 0, st, in, n, base, k, lem, u, bad);
-  else
-    hipLaunchKernelGGL(k_decompress_points<Fq>, dim3(grid(n)), dim3(TPB), 0, st, in, n, base, k, lem, u, bad);
-  HIPX(hipGetLastError());
-}
-
-double wall_ms(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 thread_local PtauChallengeTimings g_timings;
-
-void words_of(const host::U256& v, uint32_t (&w)[8]) {
-  for (int i = 0; i < 4; ++i) w[2 * i] = (uint32_t)v.w[i], w[2 * i + 1] = (uint32_t)(v.w[i] >> 32);
-}
 
 // points of section id at power N
 size_t section_points(int id, size_t N) { return id == 2 ? 2 * N - 1 : id == 6 ? 1 : N; }
-
-// The compressed sections: upload, decompress; the zkey-layout bytes into each job's out, the uncompressed
-// bytes to the hashing thread.
-void decompress_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, HashFeed& feed,
-                     Spans& sp, PtauChallengeTimings& t) {
-  pdec::Consts k1, k2;
-  pdec::fill_consts(k1, false), pdec::fill_consts(k2, true);
-  auto finish = [&](size_t k) {
-    const auto t0 = std::chrono::steady_clock::now();
-    Slot& s = slot[k % 2];
-    const Chunk& c = chunks[k];
-    const Job& j = jobs[c.job];
-    const size_t pb = j.g2 ? 128 : 64;
-    HIPX(hipEventSynchronize(s.done));
-    if (s.hbad[0])
-      throw ZkpError(ZKP_ERR_FORMAT, "response: section " + std::to_string(j.id) + " point " + std::to_string(s.hbad[1]) +
-                                         " is not a point of the curve");
-    std::memcpy(j.out + c.start * pb, s.hlem.get(), c.m * pb);
-    feed.publish(s.henc.get(), c.m * pb);
-    t.download_ms += wall_ms(t0);
-  };
-  for (size_t k = 0; k < chunks.size(); ++k) {
-    Slot& s = slot[k % 2];
-    const Chunk& c = chunks[k];
-    const Job& j = jobs[c.job];
-    const size_t pb = j.g2 ? 128 : 64;
-    if (k >= 2) feed.wait_consumed(k - 2);  // the slot's uncompressed bytes have been hashed
-    {
-      const auto t0 = std::chrono::steady_clock::now();
-      HIPX(hipMemcpyAsync(s.c, j.in + c.start * pb / 2, c.m * pb / 2, hipMemcpyHostToDevice, s.st));
-      t.upload_ms += wall_ms(t0);
-    }
-    points_bad_reset(s.dbad, s.st);
-    sp.begin(s.st);
-    launch_decompress(j.g2, s.c, c.m, c.start, j.g2 ? k2 : k1, s.b, s.a, s.dbad, s.st);
-    sp.end(s.st, j.g2 ? &t.decomp_g2_ms : &t.decomp_g1_ms);
-    HIPX(hipMemcpyAsync(s.hbad.get(), s.dbad.get(), 16, hipMemcpyDeviceToHost, s.st));
-    HIPX(hipMemcpyAsync(s.hlem.get(), s.b.get(), c.m * pb, hipMemcpyDeviceToHost, s.st));
-    HIPX(hipMemcpyAsync(s.henc.get(), s.a.get(), c.m * pb, hipMemcpyDeviceToHost, s.st));
-    HIPX(hipEventRecord(s.done, s.st));
-    ++t.chunks;
-    if (k >= 1) finish(k - 1);
-  }
-  if (!chunks.empty()) finish(chunks.size() - 1);
-}
 
 // What an old file must be for export and import: parsed, section 7 read, not truncated.  -> whether it has
 // a contribution (then its last challenge and response hash are set)
@@ -154,66 +62,18 @@ bool read_old(const PtauFile& f, const char* verb, uint8_t challenge[64], uint8_
   return have;
 }
 
-// n points through one of the two per-point kernels, chunked on one stream
-template <class Launch>
-void points_through(int device, size_t in_pb, size_t out_pb, const uint8_t* in, size_t n, uint8_t* out, uint64_t* n_bad,
-                    uint64_t* first_bad, Launch launch) {
-  *n_bad = 0, *first_bad = POINTS_NO_BAD;
-  const size_t ch = ptau_chunk_points();
-  if (!n) return;
-  HIPX(hipSetDevice(device));
-  const size_t CH = std::min(n, ch);
-  DevBuf<> din(CH * in_pb / 4), dout(CH * out_pb / 4);
-  DevBuf<unsigned long long> dbad(2);
-  Stream st(hipStreamNonBlocking);
-  points_bad_reset(dbad, st);
-  for (size_t at = 0; at < n; at += CH) {
-    const size_t m = std::min(CH, n - at);
-    HIPX(hipMemcpyAsync(din, in + at * in_pb, m * in_pb, hipMemcpyHostToDevice, st));
-    launch(din.get(), m, at, dout.get(), dbad.get(), st);
-    HIPX(hipMemcpyAsync(out + at * out_pb, dout, m * out_pb, hipMemcpyDeviceToHost, st));
-    HIPX(hipStreamSynchronize(st));  // the next upload overwrites din
-  }
-  unsigned long long h[2];
-  HIPX(hipMemcpyAsync(h, dbad, 16, hipMemcpyDeviceToHost, st));
-  HIPX(hipStreamSynchronize(st));
-  *n_bad = h[0], *first_bad = h[1];
-}
-
 }  // namespace
-
-void pstream::launch_decode(bool g2, const uint32_t* d_in, size_t n, uint64_t base, uint32_t* d_lem, unsigned long long* bad,
-                            hipStream_t st) {
-  if (!n) return;
-  ToZkey k;
-  pscale::fill_to_zkey(k.w);
-  if (g2)
-    hipLaunchKernelGGL(k_decode_points<Fq2>, dim3(grid(n)), dim3(TPB), 0, st, d_in, n, base, k, d_lem, bad);
-  else
-    hipLaunchKernelGGL(k_decode_points<Fq>, dim3(grid(n)), dim3(TPB), 0, st, d_in, n, base, k, d_lem, bad);
-  HIPX(hipGetLastError());
-}
 
 PtauChallengeTimings& ptau_challenge_timings() { return g_timings; }
 
 void points_decompress(int device, bool g2, const uint8_t* compressed, size_t n, uint8_t* out_lem, uint64_t* n_bad,
                        uint64_t* first_bad) {
-  pdec::Consts k;
-  pdec::fill_consts(k, g2);
-  const size_t pb = g2 ? 128 : 64;
-  points_through(device, pb / 2, pb, compressed, n, out_lem, n_bad, first_bad,
-                 [&](const uint32_t* in, size_t m, uint64_t base, uint32_t* out, unsigned long long* bad, hipStream_t st) {
-                   launch_decompress(g2, in, m, base, k, out, nullptr, bad, st);
-                 });
+  points_to_zkey(device, g2, true, compressed, n, out_lem, n_bad, first_bad);
 }
 
 void points_from_uncompressed(int device, bool g2, const uint8_t* bytes, size_t n, uint8_t* out_lem, uint64_t* n_bad,
                               uint64_t* first_bad) {
-  const size_t pb = g2 ? 128 : 64;
-  points_through(device, pb, pb, bytes, n, out_lem, n_bad, first_bad,
-                 [&](const uint32_t* in, size_t m, uint64_t base, uint32_t* out, unsigned long long* bad, hipStream_t st) {
-                   launch_decode(g2, in, m, base, out, bad, st);
-                 });
+  points_to_zkey(device, g2, false, bytes, n, out_lem, n_bad, first_bad);
 }
 
 void field_sqrt(int device, bool fq2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* is_square) {
@@ -351,7 +211,7 @@ std::vector<uint8_t> ptau_challenge_contribute(int device, const uint8_t* challe
   Slot slot[2];
   make_slots(slot, jobs, ch, true);
   Spans sp;
-  scale_pass(slot, jobs, chunks, wb, nullptr, ZKP_ERR_FORMAT, "challenge: ", sp, t, &t.decode_ms);
+  decode_scale_pass(slot, jobs, chunks, wb, sp, t);
   for (Slot& s : slot) HIPX(hipStreamSynchronize(s.st));
   sp.collect();
   hashed.get();

@@ -23,107 +23,28 @@
 // The same holds at the start: a file without contributions answers first_challenge(ceremonyPower), which the
 // partial hash begins with; the thread that runs the partial hash computes it first.
 //
-// The working set is the two slots' chunk buffers, on the device and pinned on the host.
-#include <algorithm>
+// The working set is the two slots' chunk buffers, on the device and pinned on the host.  The passes, the
+// slots and the kernels are ptau_stream.hip; this unit holds the two commands and points_scale_powers.
 #include <chrono>
-#include <condition_variable>
-#include <cstdlib>
 #include <cstring>
 #include <future>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "hip_check.hpp"
-#include "hip_raii.hpp"
 #include "host_ec.hpp"
 #include "prover.hpp"
 #include "ptau_contribute.hpp"
-#include "ptau_scale_kernels.hpp"
 #include "ptau_stream.hpp"
 #include "ptau_verify.hpp"
 #include "spans.hpp"
-#include "zkey_verify.hpp"
 
 namespace zkp {
 
-using pscale::Powers;
 using namespace pstream;
 
 namespace {
-
-// window bits of the ladder (gfft::scale): 2 measured 24 % (G1) and 44 % (G2) faster than 1 at power 20
-// (profiles/ptau_contribute.json); ZKP_PTAU_WINDOW=1|2 overrides the default
-constexpr int DEFAULT_WINDOW = 2;
-constexpr int TPB = 128;
-unsigned grid(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-
-// One thread per point: out_i = (base * ratio^i) * in_i as the streams that are asked for (null: skipped).
-template <class F, int WB>
-__global__ __launch_bounds__(TPB) void k_scale_powers(const uint32_t* __restrict__ in, size_t n, Powers pw,
-                                                      uint32_t* __restrict__ lem, uint32_t* __restrict__ u,
-                                                      uint32_t* __restrict__ c) {
-  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  const Xyzz<F> r = pscale::scale_lane<F, WB>(in, pw, i);
-  pscale::encode_xyzz<F>(r, pw.to_zkey, lem, u, c, i);
-}
-
-struct alignas(16) ToZkey {
-  uint32_t w[8];
-};
-
-// One thread per zkey-layout point (canonical): its other encodings
-template <class F>
-__global__ __launch_bounds__(TPB) void k_encode_points(const uint32_t* __restrict__ in, size_t n, ToZkey k,
-                                                       uint32_t* __restrict__ lem, uint32_t* __restrict__ u,
-                                                       uint32_t* __restrict__ c) {
-  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  pscale::encode_lem<F>(in, k.w, lem, u, c, i);
-}
-
-}  // namespace
-
-int pstream::window_bits() {
-  const char* e = std::getenv("ZKP_PTAU_WINDOW");
-  if (!e || !*e) return DEFAULT_WINDOW;
-  if ((e[0] != '1' && e[0] != '2') || e[1])
-    throw ZkpError(ZKP_ERR_INVALID_ARG, std::string("ZKP_PTAU_WINDOW: 1 or 2 (got '") + e + "')");
-  return e[0] - '0';
-}
-
-namespace {
-
-void launch_scale(bool g2, int wb, const uint32_t* in, size_t n, const Powers& pw, uint32_t* lem, uint32_t* u, uint32_t* c,
-                  hipStream_t st) {
-  if (!n) return;
-  const dim3 g(grid(n)), b(TPB);
-  if (g2 && wb == 2)
-    hipLaunchKernelGGL((k_scale_powers<Fq2, 2>), g, b, 0, st, in, n, pw, lem, u, c);
-  else if (g2)
-    hipLaunchKernelGGL((k_scale_powers<Fq2, 1>), g, b, 0, st, in, n, pw, lem, u, c);
-  else if (wb == 2)
-    hipLaunchKernelGGL((k_scale_powers<Fq, 2>), g, b, 0, st, in, n, pw, lem, u, c);
-  else
-    hipLaunchKernelGGL((k_scale_powers<Fq, 1>), g, b, 0, st, in, n, pw, lem, u, c);
-  HIPX(hipGetLastError());
-}
-
-void launch_encode(bool g2, const uint32_t* in, size_t n, const ToZkey& k, uint32_t* lem, uint32_t* u, uint32_t* c,
-                   hipStream_t st) {
-  if (!n) return;
-  if (g2)
-    hipLaunchKernelGGL(k_encode_points<Fq2>, dim3(grid(n)), dim3(TPB), 0, st, in, n, k, lem, u, c);
-  else
-    hipLaunchKernelGGL(k_encode_points<Fq>, dim3(grid(n)), dim3(TPB), 0, st, in, n, k, lem, u, c);
-  HIPX(hipGetLastError());
-}
-
-double wall_ms(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 thread_local PtauContributeTimings g_timings;
 
@@ -131,214 +52,12 @@ thread_local PtauContributeTimings g_timings;
 void reduced_words(const uint8_t* le32, uint32_t (&w)[8]) {
   host::U256 v = host::u256_from_le(le32);
   while (host::u256_geq(v, host::FR_DESC.mod)) host::u256_sub(v, host::FR_DESC.mod);
-  for (int i = 0; i < 4; ++i) w[2 * i] = (uint32_t)v.w[i], w[2 * i + 1] = (uint32_t)(v.w[i] >> 32);
-}
-void words_of(const host::U256& v, uint32_t (&w)[8]) {
-  for (int i = 0; i < 4; ++i) w[2 * i] = (uint32_t)v.w[i], w[2 * i + 1] = (uint32_t)(v.w[i] >> 32);
+  words_of(v, w);
 }
 
 }  // namespace
 
-void HashFeed::publish(const uint8_t* p, size_t len) {
-  {
-    std::lock_guard<std::mutex> g(m_);
-    items_.push_back({p, len});
-  }
-  cv_.notify_all();
-}
-void HashFeed::close() {
-  {
-    std::lock_guard<std::mutex> g(m_);
-    closed_ = true;
-  }
-  cv_.notify_all();
-}
-void HashFeed::wait_consumed(size_t k) {
-  std::unique_lock<std::mutex> g(m_);
-  cv_.wait(g, [&] { return done_ > k || ended_; });
-}
-void HashFeed::end() {
-  {
-    std::lock_guard<std::mutex> g(m_);
-    ended_ = true;
-  }
-  cv_.notify_all();
-}
-void HashFeed::drain(Blake2b& h) {
-  for (;;) {
-    std::pair<const uint8_t*, size_t> it;
-    {
-      std::unique_lock<std::mutex> g(m_);
-      cv_.wait(g, [&] { return done_ < items_.size() || closed_; });
-      if (done_ == items_.size()) return;
-      it = items_[done_];
-    }
-    h.update(it.first, it.second);
-    {
-      std::lock_guard<std::mutex> g(m_);
-      ++done_;
-    }
-    cv_.notify_all();
-  }
-}
-
-std::vector<Chunk> pstream::chunks_of(const std::vector<Job>& jobs, size_t ch) {
-  std::vector<Chunk> v;
-  for (size_t j = 0; j < jobs.size(); ++j)
-    for (size_t at = 0; at < jobs[j].n; at += ch) v.push_back(Chunk{(int)j, at, std::min(ch, jobs[j].n - at)});
-  return v;
-}
-
-void pstream::make_slots(Slot (&slot)[2], const std::vector<Job>& jobs, size_t ch, bool hashes) {
-  size_t bytes = 0;
-  for (const Job& j : jobs) bytes = std::max(bytes, std::min(ch, j.n) * (j.g2 ? 128 : 64));
-  for (Slot& s : slot) {
-    s.st = Stream(hipStreamNonBlocking);
-    s.a = DevBuf<>(bytes / 4), s.b = DevBuf<>(bytes / 4);
-    s.dbad = DevBuf<unsigned long long>(2);
-    s.hlem = PinnedBuf<uint8_t>(bytes);
-    s.hbad = PinnedBuf<unsigned long long>(2);
-    s.done = Event(false);
-    if (hashes) s.c = DevBuf<>(bytes / 8), s.henc = PinnedBuf<uint8_t>(bytes);
-  }
-}
-
-// Pass 1 over the chunks (ptau_stream.hpp)
-void pstream::scale_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, int wb,
-                         HashFeed* feed, zkp_status bad_status, const char* bad_prefix, Spans& sp, PtauContributeTimings& t,
-                         double* decode_ms) {
-  bool enc = feed != nullptr;
-  for (const Job& j : jobs) enc = enc || j.out_enc;
-  auto finish = [&](size_t k) {
-    const auto t0 = std::chrono::steady_clock::now();
-    Slot& s = slot[k % 2];
-    const Chunk& c = chunks[k];
-    const Job& j = jobs[c.job];
-    const size_t pb = j.g2 ? 128 : 64;
-    HIPX(hipEventSynchronize(s.done));
-    if (s.hbad[0])
-      throw ZkpError(bad_status, std::string(bad_prefix) + (j.id ? "section " + std::to_string(j.id) + " " : "") + "point " +
-                                     std::to_string(s.hbad[1]) + " is not on the curve");
-    if (j.out) std::memcpy(j.out + c.start * pb, s.hlem.get(), c.m * pb);
-    if (j.out_enc) std::memcpy(j.out_enc + c.start * pb / 2, s.henc.get(), c.m * pb / 2);
-    if (feed) feed->publish(s.henc.get(), c.m * pb / 2);
-    t.download_ms += wall_ms(t0);
-  };
-  for (size_t k = 0; k < chunks.size(); ++k) {
-    Slot& s = slot[k % 2];
-    const Chunk& c = chunks[k];
-    const Job& j = jobs[c.job];
-    const size_t pb = j.g2 ? 128 : 64;
-    if (feed && k >= 2) feed->wait_consumed(k - 2);  // the slot's compressed bytes have been hashed
-    Powers pw;
-    pscale::fill_powers(pw, j.first, j.ratio, c.start);
-    {
-      const auto t0 = std::chrono::steady_clock::now();
-      HIPX(hipMemcpyAsync(decode_ms ? s.b : s.a, j.in + c.start * pb, c.m * pb, hipMemcpyHostToDevice, s.st));
-      t.upload_ms += wall_ms(t0);
-    }
-    points_bad_reset(s.dbad, s.st);
-    if (decode_ms) {  // b is free until the scaling writes it: the staging buffer of the uncompressed bytes
-      sp.begin(s.st);
-      launch_decode(j.g2, s.b, c.m, c.start, s.a, s.dbad, s.st);
-      sp.end(s.st, decode_ms);
-    }
-    sp.begin(s.st);
-    points_check_resident(j.g2, s.a, c.m, c.start, s.dbad, s.st);
-    sp.end(s.st, &t.parse_check_ms);
-    sp.begin(s.st);
-    launch_scale(j.g2, wb, s.a, c.m, pw, j.out ? s.b.get() : nullptr, nullptr, enc ? s.c.get() : nullptr, s.st);
-    sp.end(s.st, j.g2 ? &t.g2_ms : &t.g1_ms);
-    HIPX(hipMemcpyAsync(s.hbad.get(), s.dbad.get(), 16, hipMemcpyDeviceToHost, s.st));
-    if (j.out) HIPX(hipMemcpyAsync(s.hlem.get(), s.b.get(), c.m * pb, hipMemcpyDeviceToHost, s.st));
-    if (enc) HIPX(hipMemcpyAsync(s.henc.get(), s.c.get(), c.m * pb / 2, hipMemcpyDeviceToHost, s.st));
-    HIPX(hipEventRecord(s.done, s.st));
-    ++t.chunks;
-    if (k >= 1) finish(k - 1);
-  }
-  if (!chunks.empty()) finish(chunks.size() - 1);
-}
-
-// Pass 2: the new sections uncompressed, to the hashing thread (ptau_stream.hpp)
-void pstream::encode_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, HashFeed& feed,
-                          Spans& sp, PtauContributeTimings& t, bool from_in) {
-  ToZkey tz;
-  pscale::fill_to_zkey(tz.w);
-  auto finish = [&](size_t k) {
-    const auto t0 = std::chrono::steady_clock::now();
-    Slot& s = slot[k % 2];
-    const Chunk& c = chunks[k];
-    const Job& j = jobs[c.job];
-    const size_t pb = j.g2 ? 128 : 64;
-    HIPX(hipEventSynchronize(s.done));
-    if (j.out_enc) std::memcpy(j.out_enc + c.start * pb, s.henc.get(), c.m * pb);
-    feed.publish(s.henc.get(), c.m * pb);
-    t.download_ms += wall_ms(t0);
-  };
-  for (size_t k = 0; k < chunks.size(); ++k) {
-    Slot& s = slot[k % 2];
-    const Chunk& c = chunks[k];
-    const Job& j = jobs[c.job];
-    const size_t pb = j.g2 ? 128 : 64;
-    if (k >= 2) feed.wait_consumed(k - 2);
-    {
-      const auto t0 = std::chrono::steady_clock::now();
-      HIPX(hipMemcpyAsync(s.a, (from_in ? j.in : j.out) + c.start * pb, c.m * pb, hipMemcpyHostToDevice, s.st));
-      t.upload_ms += wall_ms(t0);
-    }
-    sp.begin(s.st);
-    launch_encode(j.g2, s.a, c.m, tz, nullptr, s.b, nullptr, s.st);
-    sp.end(s.st, &t.encode_ms);
-    HIPX(hipMemcpyAsync(s.henc.get(), s.b.get(), c.m * pb, hipMemcpyDeviceToHost, s.st));
-    HIPX(hipEventRecord(s.done, s.st));
-    if (k >= 1) finish(k - 1);
-  }
-  if (!chunks.empty()) finish(chunks.size() - 1);
-}
-
-void pstream::ptau_layout(const PtauFile& f, std::vector<uint8_t>& out, uint8_t* (&sec_out)[8]) {
-  size_t body = 12 + 12 + f.sec[1].len;
-  for (int id = 2; id <= 6; ++id) body += 12 + f.sec[id].len;
-  out.reserve(body + 12 + f.sec[7].len + 2048);  // section 7 with its new record is appended: no reallocation
-  out.resize(body);
-  uint8_t* o = out.data();
-  auto put32 = [&](uint32_t x) { std::memcpy(o, &x, 4), o += 4; };
-  auto put64 = [&](uint64_t x) { std::memcpy(o, &x, 8), o += 8; };
-  std::memcpy(o, "ptau", 4), o += 4;
-  put32(1), put32(7);
-  put32(1), put64(f.sec[1].len);
-  std::memcpy(o, f.sec[1].ptr, f.sec[1].len), o += f.sec[1].len;
-  for (int id = 2; id <= 6; ++id) {
-    put32((uint32_t)id), put64(f.sec[id].len);
-    sec_out[id] = o, o += f.sec[id].len;
-  }
-}
-
-// section 7: the count, the earlier records, the new one
-void pstream::ptau_append_section7(const PtauFile& f, std::vector<uint8_t>& out, const std::vector<uint8_t>& rec) {
-  const size_t old = f.sec[7].len - 4, s7 = 4 + old + rec.size();
-  uint32_t count;
-  std::memcpy(&count, f.sec[7].ptr, 4);
-  ++count;
-  const uint32_t id = 7;
-  const uint64_t l64 = s7;
-  auto app = [&](const void* p, size_t n) { out.insert(out.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
-  app(&id, 4), app(&l64, 8), app(&count, 4), app(f.sec[7].ptr + 4, old), app(rec.data(), rec.size());
-}
-
 PtauContributeTimings& ptau_contribute_timings() { return g_timings; }
-
-size_t ptau_chunk_points() {
-  constexpr size_t DEFAULT = size_t(1) << 22, MAX = size_t(1) << 26;
-  const char* e = std::getenv("ZKP_PTAU_CHUNK");
-  if (!e) return DEFAULT;
-  char* stop = nullptr;
-  const long long v = std::strtoll(e, &stop, 10);
-  if (!*e || *stop || v < 1 || (unsigned long long)v > MAX)
-    throw ZkpError(ZKP_ERR_INVALID_ARG, "ZKP_PTAU_CHUNK: points per chunk must be an integer within 1.." +
-                                            std::to_string(MAX) + " (got '" + e + "')");
-  return (size_t)v;
-}
 
 void points_scale_powers(int device, bool g2, const uint8_t* points, size_t n, const uint8_t* first32,
                          const uint8_t* ratio32, uint8_t* out) {

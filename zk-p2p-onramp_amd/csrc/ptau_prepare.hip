@@ -103,10 +103,6 @@ __global__ __launch_bounds__(Geom<F>::TPB) void k_gfft_affine(const uint32_t* __
   gfft::finish<F>(load_xyzz<F>(work, (size_t)blockIdx.y * n + i), tw, v.out[blockIdx.y], (n - 1) + i);
 }
 
-double wall_ms(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 thread_local PrepareTimings g_timings;
 
 // words of XYZZ work space for nvec vectors of levels up to `power` (none if every level is small)

@@ -15,7 +15,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
-#include <fstream>
 #include <memory>
 #include <vector>
 
@@ -23,6 +22,7 @@
 #include "device_pipeline.hpp"
 #include "g2_subgroup_kernels.hpp"
 #include "mpc.hpp"
+#include "points_through.hpp"
 #include "ptau_verify.hpp"
 #include "qap.hpp"
 #include "spans.hpp"
@@ -53,10 +53,6 @@ __global__ __launch_bounds__(TPB) void k_fr_add_into(uint32_t* __restrict__ s, c
   const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
   if (i >= n) return;
   store_fe(s + i * 8, add(load_fe<FrCfg>(s + i * 8), load_fe<FrCfg>(t + i * 8)));
-}
-
-double wall_ms(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 thread_local PtauVerifyTimings g_timings;
@@ -161,11 +157,6 @@ bool same_jac(const Jac<F>& a, const Jac<F>& b) {
   return x.inf == y.inf && (x.inf || (x.x == y.x && x.y == y.y));
 }
 
-void os_seed(uint8_t seed[32]) {
-  std::ifstream f("/dev/urandom", std::ios::binary);
-  if (!f.read(reinterpret_cast<char*>(seed), 32)) throw ZkpError(ZKP_ERR_IO, "cannot read /dev/urandom");
-}
-
 // zkey-layout bytes (Montgomery 2^256, the host's own form) -> host points; canonical, checked before
 Affine<HFq> g1_of(const uint8_t* p) {
   return Affine<HFq>{HFq::raw(host::u256_from_le(p)), HFq::raw(host::u256_from_le(p + 32)), false};
@@ -249,21 +240,10 @@ void g2_subgroup_check(int device, const uint8_t* points, size_t n, uint64_t* n_
   *n_bad = 0, *first_bad = SUBGROUP_NO_BAD;
   if (!n) return;
   HIPX(hipSetDevice(device));
-  Stream st(hipStreamNonBlocking);
-  const size_t CH = std::min(n, verify_chunk_points());
-  DevBuf<> d(CH * 32);
-  DevBuf<unsigned long long> dbad(2);
-  points_bad_reset(dbad, st);
-  for (size_t at = 0; at < n; at += CH) {
-    const size_t m = std::min(CH, n - at);
-    HIPX(hipMemcpyAsync(d, points + at * 128, m * 128, hipMemcpyHostToDevice, st));
-    g2_subgroup_resident(d, m, at, dbad, st);
-    HIPX(hipStreamSynchronize(st));  // the next upload overwrites d
-  }
-  unsigned long long h[2];
-  HIPX(hipMemcpyAsync(h, dbad, 16, hipMemcpyDeviceToHost, st));
-  HIPX(hipStreamSynchronize(st));
-  *n_bad = h[0], *first_bad = h[1];
+  points_through(verify_chunk_points(), 128, 0, points, n, nullptr, n_bad, first_bad,
+                 [](const uint32_t* d, size_t m, uint64_t base, uint32_t*, unsigned long long* bad, hipStream_t st) {
+                   g2_subgroup_resident(d, m, base, bad, st);
+                 });
 }
 
 PairSums rlc_pairs(int device, bool g2, const uint8_t* seed32, uint64_t first_index, const uint8_t* points, size_t n) {
@@ -319,7 +299,7 @@ bool ptau_verify_sections(int device, const uint8_t* ptau, size_t len, const uin
   if (seed32)
     std::memcpy(seed, seed32, 32);
   else
-    os_seed(seed);
+    os_random(seed, 32);
   t.parse_ms = wall_ms(t_begin);
 
   // ---- device: the working set first

@@ -1,11 +1,18 @@
-// Device time of stretches of one stream's work, summed per stage (ptau_prepare.hip, ptau_verify.hip).
+// Device time of stretches of one stream's work, summed per stage, and the host's wall time beside it: the
+// two clocks of every timing vector.
 #pragma once
+#include <chrono>
 #include <vector>
 
 #include "hip_check.hpp"
 #include "hip_raii.hpp"
 
 namespace zkp {
+
+// host ms since t0
+inline double wall_ms(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // device ms between pairs of events, read once everything is complete
 struct Spans {

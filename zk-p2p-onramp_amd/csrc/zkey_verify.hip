@@ -16,7 +16,9 @@
 #include "curve.hpp"
 #include "device_pipeline.hpp"
 #include "mpc.hpp"
+#include "points_through.hpp"
 #include "qap.hpp"
+#include "spans.hpp"
 #include "zkey_verify.hpp"
 
 namespace zkp {
@@ -153,10 +155,6 @@ void check_index_range(uint64_t first_index, size_t n) {
     throw ZkpError(ZKP_ERR_INVALID_ARG, "rlc: coefficient index out of range");
 }
 
-double wall_ms(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 // window bits for n uniform 128-bit scalars at depth 1: lg n - 3 as the kernel-level MSMs take, moved
@@ -219,22 +217,11 @@ void points_check(int device, bool g2, const uint8_t* points, size_t n, uint64_t
   *n_bad = 0, *first_bad = RLC_NO_BAD;
   if (!n) return;
   HIPX(hipSetDevice(device));
-  Stream st(hipStreamNonBlocking);
-  const size_t pb = g2 ? 128 : 64, CH = std::min(n, verify_chunk_points());
-  DevBuf<> d(CH * pb / 4);
-  DevBuf<unsigned long long> dbad(2);
   const CurveB b = curve_b(g2);
-  reset_bad(dbad, 1, st);
-  for (size_t at = 0; at < n; at += CH) {
-    const size_t m = std::min(CH, n - at);
-    HIPX(hipMemcpyAsync(d, points + at * pb, m * pb, hipMemcpyHostToDevice, st));
-    launch_check(g2, d, m, at, b, dbad, st);
-    HIPX(hipStreamSynchronize(st));  // the next upload overwrites d
-  }
-  unsigned long long h[2];
-  HIPX(hipMemcpyAsync(h, dbad, 16, hipMemcpyDeviceToHost, st));
-  HIPX(hipStreamSynchronize(st));
-  *n_bad = h[0], *first_bad = h[1];
+  points_through(verify_chunk_points(), g2 ? 128 : 64, 0, points, n, nullptr, n_bad, first_bad,
+                 [&](const uint32_t* d, size_t m, uint64_t base, uint32_t*, unsigned long long* bad, hipStream_t st) {
+                   launch_check(g2, d, m, base, b, bad, st);
+                 });
 }
 
 void points_bad_reset(unsigned long long* bad, hipStream_t st) { reset_bad(bad, 1, st); }
