@@ -553,6 +553,60 @@ zkp_status zkp_points_from_uncompressed(int device, int g2, const uint8_t* bytes
                                         uint64_t* first_bad);
 zkp_status zkp_field_sqrt(int device, int fq2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* is_square);
 
+/* `wtns check <circuit.r1cs> <witness.wtns>`: does the witness satisfy every constraint A.w * B.w = C.w of
+ * the circuit, and if not, which ones fail.  Later snarkjs versions ship this command and circom_tester's
+ * checkConstraints is the same test; both recalled, unpinned (the reference pins snarkjs 0.4.22, which has
+ * neither), so the shape is restated and the words are ours.  The zkey holds A and B only: the .r1cs is
+ * the one file with C.  On the device the check is one sparse matrix-vector product in Fr and a comparison
+ * per constraint.
+ *
+ * A checker holds the circuit's matrices on `device` (loaded and converted once).  A malformed .r1cs
+ * (bad magic or version, a truncated section, a wire index >= nWires, more than 2^32 - 1 terms:
+ * ZKP_ERR_FORMAT; n8 != 32 or a prime other than bn128's r: ZKP_ERR_CURVE) fails before any device work.
+ * One check at a time per checker (a mutex serialises concurrent callers).
+ *
+ * A check's status reports only a malformed witness file (ZKP_ERR_FORMAT / ZKP_ERR_CURVE as zkp_prove;
+ * ZKP_ERR_WITNESS_LENGTH when its length is not the circuit's nWires) or a device error.  The verdict is
+ * ZKP_OK with res->valid and a message (msg may be NULL; at most msg_cap - 1 characters and a NUL):
+ *   "OK"                                                           valid = 1
+ *   "INVALID: signal 0 is not 1"
+ *   "INVALID: signal <i> is not reduced"                           the lowest i with a value >= r
+ *   "INVALID: constraint <first_bad> is not satisfied (<n_bad> of <n> fail)"
+ * in this order of precedence.  n_bad is the exact number of failing constraints, bad[] the lowest
+ * n_listed = min(16, n_bad) of them in ascending order, first_bad = bad[0]; all zero unless the verdict is
+ * the last one.  The result is a function of the input alone. */
+typedef struct zkp_checker zkp_checker;
+typedef struct zkp_check_result {
+  int valid;
+  uint64_t n_bad, first_bad, n_constraints;
+  uint32_t n_listed;
+  uint64_t bad[16];
+} zkp_check_result;
+zkp_status zkp_checker_load(int device, const uint8_t* r1cs, size_t len, zkp_checker** out);
+/* any of the four may be NULL; n_vars = nWires, n_terms = the terms of A, B and C together */
+zkp_status zkp_checker_info(const zkp_checker* c, uint32_t* n_vars, uint32_t* n_public, uint32_t* n_constraints,
+                            uint64_t* n_terms);
+zkp_status zkp_checker_check(zkp_checker* c, const uint8_t* wtns, size_t len, zkp_check_result* res, char* msg,
+                             size_t msg_cap);
+/* The witness zkp_witness_stage left in slot `slot` of p's device dev_index, read in place (no second
+ * transfer): stage -> check -> zkp_prove_staged.  The checker must be on that device and the circuit's
+ * nWires equal the key's nVars (else ZKP_ERR_INVALID_ARG, as an empty slot).  Holds the staging slots as
+ * a staged proof does (a restage waits for it) and only reads the slot. */
+zkp_status zkp_checker_check_staged(zkp_checker* c, zkp_prover* p, int dev_index, int slot, zkp_check_result* res,
+                                    char* msg, size_t msg_cap);
+void zkp_checker_free(zkp_checker* c);
+/* load + check + free.  Both files are validated before any device work. */
+zkp_status zkp_wtns_check(int device, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* wtns, size_t wtns_len,
+                          zkp_check_result* res, char* msg, size_t msg_cap);
+/* ms of the calling thread's last zkp_wtns_check / zkp_checker_load / zkp_checker_check[_staged]:
+ * [0] r1cs parse + CSR + row classification (host), [1] CSR upload + coefficient conversion, [2] witness
+ * copy (HIP events), [3] the kernels and the result's copy back (HIP events), [4] host wall of the call.
+ * A load fills [0] [1] [4] (the rest 0), a check [2] [3] [4], zkp_wtns_check all five.  n = capacity. */
+zkp_status zkp_wtns_check_timings(double* ms, int n);
+/* [0] constraints on the wavefront-per-constraint kernel, [1] the term count from which a constraint takes
+ * it (ZKP_WTNS_CHECK_LONG at load overrides the default; 0: none does).  n = capacity. */
+zkp_status zkp_checker_paths(const zkp_checker* c, uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -28,6 +30,7 @@
 #include "ptau_challenge.hpp"
 #include "ptau_contribute.hpp"
 #include "ptau_verify.hpp"
+#include "wtns_check.hpp"
 #include "zkey_io.hpp"
 #include "zkey_verify.hpp"
 
@@ -896,6 +899,109 @@ zkp_status zkp_bench_ntt(int device, int log_n, int warmup, int iters, double* m
 zkp_status zkp_bench_ntt_batch(int device, int log_n, int count, int warmup, int iters, double* ms) {
   if (!ms || log_n < 1 || log_n > 27 || count < 1 || count > 3) return fail(ZKP_ERR_INVALID_ARG, "bad argument");
   return guard([&] { *ms = zkp::bench_ntt(device, log_n, count, warmup, iters); });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- wtns check (wtns_check.hpp)
+
+struct zkp_checker {
+  zkp::WitnessChecker* impl;
+};
+
+namespace {
+void clear_result(zkp_check_result* res, char* msg, size_t msg_cap) {
+  std::memset(res, 0, sizeof(*res));
+  put_msg("", msg, msg_cap);
+}
+}  // namespace
+
+extern "C" {
+
+zkp_status zkp_checker_load(int device, const uint8_t* r1cs, size_t len, zkp_checker** out) {
+  if (!r1cs || !len || !out) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  *out = nullptr;
+  return guard([&] {
+    double parse_ms = 0;
+    zkp::R1csCsr csr = zkp::parse_r1cs_or_throw(r1cs, len, &parse_ms);
+    std::unique_ptr<zkp::WitnessChecker> w(new zkp::WitnessChecker(device, std::move(csr), parse_ms));
+    *out = new zkp_checker{w.get()};
+    w.release();
+  });
+}
+
+zkp_status zkp_checker_info(const zkp_checker* c, uint32_t* n_vars, uint32_t* n_public, uint32_t* n_constraints,
+                            uint64_t* n_terms) {
+  if (!c) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  if (n_vars) *n_vars = c->impl->n_wires();
+  if (n_public) *n_public = c->impl->n_public();
+  if (n_constraints) *n_constraints = c->impl->n_constraints();
+  if (n_terms) *n_terms = c->impl->n_terms();
+  return ZKP_OK;
+}
+
+zkp_status zkp_checker_paths(const zkp_checker* c, uint64_t* out, int n) {
+  if (!c || !out || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const uint64_t v[2] = {c->impl->n_long(), c->impl->long_terms()};
+  for (int i = 0; i < n && i < 2; ++i) out[i] = v[i];
+  return ZKP_OK;
+}
+
+zkp_status zkp_checker_check(zkp_checker* c, const uint8_t* wtns, size_t len, zkp_check_result* res, char* msg,
+                             size_t msg_cap) {
+  if (!c || !wtns || !len || !res) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  clear_result(res, msg, msg_cap);
+  return guard([&] {
+    std::string m;
+    c->impl->check(wtns, len, res, m);
+    put_msg(m, msg, msg_cap);
+  });
+}
+
+zkp_status zkp_checker_check_staged(zkp_checker* c, zkp_prover* p, int dev_index, int slot, zkp_check_result* res,
+                                    char* msg, size_t msg_cap) {
+  if (!c || !p || !res) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  clear_result(res, msg, msg_cap);
+  return guard([&] {
+    std::string m;
+    c->impl->check_staged(*p->impl, dev_index, slot, res, m);
+    put_msg(m, msg, msg_cap);
+  });
+}
+
+void zkp_checker_free(zkp_checker* c) {
+  if (!c) return;
+  delete c->impl;
+  delete c;
+}
+
+zkp_status zkp_wtns_check(int device, const uint8_t* r1cs, size_t r1cs_len, const uint8_t* wtns, size_t wtns_len,
+                          zkp_check_result* res, char* msg, size_t msg_cap) {
+  if (!r1cs || !r1cs_len || !wtns || !wtns_len || !res) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  clear_result(res, msg, msg_cap);
+  return guard([&] {
+    const auto t0 = std::chrono::steady_clock::now();
+    double parse_ms = 0;
+    zkp::R1csCsr csr = zkp::parse_r1cs_or_throw(r1cs, r1cs_len, &parse_ms);
+    zkp::check_wtns_header(csr, wtns, wtns_len);  // both files are sound before the device is touched
+    zkp::WitnessChecker w(device, std::move(csr), parse_ms);
+    const zkp::CheckTimings load = zkp::check_timings();
+    std::string m;
+    w.check(wtns, wtns_len, res, m);
+    put_msg(m, msg, msg_cap);
+    zkp::CheckTimings& t = zkp::check_timings();
+    t.parse_ms = load.parse_ms;
+    t.upload_ms = load.upload_ms;
+    t.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  });
+}
+
+zkp_status zkp_wtns_check_timings(double* ms, int n) {
+  if (!ms || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const zkp::CheckTimings& t = zkp::check_timings();
+  const double v[5] = {t.parse_ms, t.upload_ms, t.copy_ms, t.kernel_ms, t.total_ms};
+  for (int i = 0; i < n && i < 5; ++i) ms[i] = v[i];
+  return ZKP_OK;
 }
 
 }  // extern "C"

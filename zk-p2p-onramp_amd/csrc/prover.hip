@@ -511,6 +511,16 @@ void Prover::prove_staged(int dev, int slot, const uint8_t* r32, const uint8_t* 
   record_timings(last_ms_, m, host_ms);
 }
 
+Prover::StagedView Prover::staged_view(int dev, int slot) const {
+  DevicePipeline& base = staged_pipeline(dev);
+  StagedView v;
+  v.hold = base.hold_stage();
+  v.ptr = base.slot_ptr(slot);
+  v.n_signals = hdr_.n_vars;
+  v.device = base.device();
+  return v;
+}
+
 void Prover::set_instrument(bool on) {
   for (auto& d : devs_) d->set_instrument(on);
 }

@@ -17,6 +17,7 @@
 #include <cstdint>
 #include <memory>
 #include <mutex>
+#include <shared_mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -90,6 +91,16 @@ class Prover {
   // HBM-resident witnesses (benchmarks time the proof without the PCIe copy)
   void stage(int dev, int slot, const uint8_t* wtns, size_t len);
   void prove_staged(int dev, int slot, const uint8_t* r32, const uint8_t* s32, zkp_proof* out);
+  // read-only view of a staged witness (zkp_checker_check_staged): the slot's device pointer (32 B per
+  // signal, standard form) and signal count, under the shared hold of the staging slots that a staged
+  // proof takes -- the slot is complete (stage() waits for its copy) and is not restaged while `hold` lives
+  struct StagedView {
+    std::shared_lock<std::shared_mutex> hold;
+    const uint32_t* ptr = nullptr;
+    size_t n_signals = 0;
+    int device = -1;
+  };
+  StagedView staged_view(int dev, int slot) const;
   // per-kernel HIP-event statistics of the bucket-accumulate kernels
   void set_instrument(bool on);
   void kernel_stats(double* out, int n) const;

@@ -14,6 +14,7 @@
  *   node cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]
  * and the gate of the ceremony (reference circuit/scripts/generate_keys_phase2_groth16.sh:26):
  *   node cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>
+ *   node cli.js wtns check <circuit.r1cs> <witness.wtns> [-v]   (later snarkjs' command; recalled, unpinned)
  * and the last step of phase 1 (reference circuit/scripts/generate_keys_phase1.sh:20), whose output `zkey new` reads:
  *   node cli.js powersoftau prepare phase2 <pot_beacon.ptau> <pot_final.ptau> [-v]
  * and the check of a phase-1 file (reference circuit/scripts/generate_keys_phase1.sh:16; the step
@@ -29,7 +30,7 @@
  *   node cli.js powersoftau import response <old.ptau> <response> <new.ptau> [-n=|--name=name] [-v]
  */
 const fs = require('fs');
-const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, powersOfTau, release } = require('./groth16');
+const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, powersOfTau, wtns: wtnsApi, release } = require('./groth16');
 
 const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n' +
               '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
@@ -37,6 +38,7 @@ const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.
               '       cli.js zkey contribute <in.zkey> <out.zkey> -e=<entropy> [-n=name]\n' +
               '       cli.js zkey beacon <in.zkey> <out.zkey> <beaconHashHex> <numIterationsExp> [-n=name]\n' +
               '       cli.js zkey verify <circuit.r1cs> <pot.ptau> <circuit.zkey>\n' +
+              '       cli.js wtns check <circuit.r1cs> <witness.wtns> [-v]\n' +
               '       cli.js powersoftau prepare phase2 <in.ptau> <out.ptau> [-v]\n' +
               '       cli.js powersoftau verify <pot.ptau> [-v]\n' +
               '       cli.js powersoftau new bn128 <power> <out.ptau> [-v]\n' +
@@ -138,6 +140,20 @@ async function main(argv) {
       error: (m) => process.stdout.write(`[ERROR] snarkJS: ${m}\n`),
     };
     return (await verifyFromR1cs(named[2], named[3], named[4], logger)) ? 0 : 1;
+  }
+  if (argv[0] === 'wtns' && argv[1] === 'check') {
+    // exit 0 and "[INFO]  snarkJS: WITNESS IS CORRECT", else the verdict, "[ERROR] snarkJS: WITNESS IS NOT
+    // CORRECT" and exit 1 (the log words of later snarkjs as recalled, unpinned); -v is accepted
+    const pos = argv.filter((a) => !a.startsWith('-'));
+    if (pos.length !== 4) {
+      process.stderr.write(USAGE);
+      return 1;
+    }
+    const logger = {
+      info: (m) => process.stdout.write(`[INFO]  snarkJS: ${m}\n`),
+      error: (m) => process.stdout.write(`[ERROR] snarkJS: ${m}\n`),
+    };
+    return (await wtnsApi.check(pos[2], pos[3], logger)) ? 0 : 1;
   }
   if (argv[0] === 'zkey' && argv[1] === 'contribute') {
     const pos = argv.filter((a) => !a.startsWith('-'));

@@ -263,6 +263,29 @@ async function verifyFromInit(initName, zkeyName, logger, device, ...rest) {
 }
 
 /*
+ * `wtns.check(r1csFileName, wtnsFileName, logger)` of later snarkjs versions (the `wtns check` command;
+ * recalled, unpinned: the reference's snarkjs 0.4.22 has neither): every constraint of the .r1cs evaluated
+ * on the witness on the GPU.  Resolves to a boolean; "WITNESS IS CORRECT" goes to logger.info, the verdict
+ * ("INVALID: constraint <i> is not satisfied (<k> of <n> fail)", ...) and "WITNESS IS NOT CORRECT" to
+ * logger.error (the log words as recalled from later snarkjs, unpinned).  Malformed input rejects.
+ * checkDetails resolves to the whole verdict {valid, message, nBad, firstBad, bad, nConstraints}.
+ */
+async function wtnsCheckDetails(r1csFileName, wtnsFileName, device) {
+  return addon.wtnsCheck(readInput(r1csFileName), readInput(wtnsFileName), device || 0);
+}
+async function wtnsCheck(r1csFileName, wtnsFileName, logger, device) {
+  const res = await wtnsCheckDetails(r1csFileName, wtnsFileName, device);
+  if (logger) {
+    if (res.valid && logger.info) logger.info('WITNESS IS CORRECT');
+    if (!res.valid && logger.error) {
+      logger.error(res.message);
+      logger.error('WITNESS IS NOT CORRECT');
+    }
+  }
+  return res.valid;
+}
+
+/*
  * snarkjs' `powersOfTau.verify(tauFilename, logger)` (the `powersoftau verify` step, reference
  * circuit/scripts/generate_keys_phase1.sh:16; skipped as too slow in generate_keys_phase2_groth16.sh:3): the
  * contribution chain on the host, every point section on the GPU.  Resolves to a boolean; the failing check
@@ -399,6 +422,7 @@ module.exports = {
   zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit },
   powersOfTau: { newAccumulator, contribute: contributePtau, beacon: beaconPtau, preparePhase2, verify: verifyPtau,
                  exportChallenge, challengeContribute, importResponse },
+  wtns: { check: wtnsCheck, checkDetails: wtnsCheckDetails },
   preparePhase2,
   verifyFromR1cs,
   verifyFromInit,

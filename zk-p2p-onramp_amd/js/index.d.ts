@@ -74,6 +74,22 @@ export declare const powersOfTau: {
 export declare function preparePhase2(oldPtauName: Input, newPtauName?: string | { type: "mem"; data?: Uint8Array },
                                       logger?: Logger, device?: number): Promise<Buffer>;
 export interface VerifyLogger extends Logger { error?(msg: string): void }
+/** The verdict of `wtns check`: bad holds the lowest min(16, nBad) failing constraints in ascending order. */
+export interface WitnessCheck {
+  valid: boolean;
+  message: string;
+  nBad: number;
+  firstBad: number;
+  bad: number[];
+  nConstraints: number;
+}
+export declare const wtns: {
+  /** Later snarkjs' `wtns check <circuit.r1cs> <witness.wtns>` (recalled, unpinned): every constraint of the
+   *  circuit on the witness, on the GPU.  Logs "WITNESS IS CORRECT" (info) or the verdict and "WITNESS IS NOT
+   *  CORRECT" (error); malformed input rejects. */
+  check(r1csFileName: Input, wtnsFileName: Input, logger?: VerifyLogger, device?: number): Promise<boolean>;
+  checkDetails(r1csFileName: Input, wtnsFileName: Input, device?: number): Promise<WitnessCheck>;
+};
 export declare function verifyFromR1cs(r1csName: Input, ptauName: Input, zkeyName: Input, logger?: VerifyLogger,
                                        device?: number): Promise<boolean>;
 export declare function verifyFromInit(initName: Input, zkeyName: Input, logger?: VerifyLogger, device?: number):

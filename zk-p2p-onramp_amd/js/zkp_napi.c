@@ -22,6 +22,7 @@
  *   ptauChallengeContribute(challengeBuffer, entropy, device?, rand64?) -> Buffer (`powersoftau challenge contribute`)
  *   ptauImportResponse(ptauBuffer, responseBuffer, name?, device?) -> Buffer (`snarkjs powersoftau import response`)
  *   zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify`)
+ *   wtnsCheck(r1csBuffer, wtnsBuffer, device?) -> {valid, message, nBad, firstBad, bad, nConstraints} (`wtns check`)
  *   version()
  * prove()/proveBatch() run on the libuv threadpool (napi_async_work), so the JS main
  * thread is never blocked — the same async contract as snarkjs' Promise API.
@@ -208,6 +209,52 @@ static napi_value js_ptau_verify(napi_env env, napi_callback_info info) {
 }
 static napi_value js_zkey_verify_r1cs(napi_env env, napi_callback_info info) {
   return verify_common(env, info, 3, "zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?)");
+}
+
+/* wtnsCheck(r1csBuffer, wtnsBuffer, device?) -> {valid, message, nBad, firstBad, bad: number[], nConstraints}:
+ * `wtns check` (zkp_wtns_check), synchronous.  A witness that fails is a verdict; malformed input throws
+ * with the zkp_status as code. */
+static napi_value js_wtns_check(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  void* p[2] = {NULL, NULL};
+  size_t len[2] = {0, 0};
+  bool ok = argc >= 2;
+  for (int i = 0; ok && i < 2; ++i) {
+    bool b = false;
+    napi_is_buffer(env, argv[i], &b);
+    ok = b && napi_get_buffer_info(env, argv[i], &p[i], &len[i]) == napi_ok;
+  }
+  if (!ok) {
+    napi_throw_type_error(env, NULL, "wtnsCheck(r1csBuffer, wtnsBuffer, device?)");
+    return NULL;
+  }
+  int device = 0;
+  if (argc > 2) napi_get_value_int32(env, argv[2], &device);
+  zkp_check_result r;
+  char msg[256];
+  zkp_status st = zkp_wtns_check(device, (const uint8_t*)p[0], len[0], (const uint8_t*)p[1], len[1], &r, msg, sizeof msg);
+  if (st != ZKP_OK) return throw_status(env, st);
+  napi_value res, v, m, bad;
+  NAPI_CALL(env, napi_create_object(env, &res));
+  NAPI_CALL(env, napi_get_boolean(env, r.valid != 0, &v));
+  NAPI_CALL(env, napi_set_named_property(env, res, "valid", v));
+  NAPI_CALL(env, napi_create_string_utf8(env, msg, NAPI_AUTO_LENGTH, &m));
+  NAPI_CALL(env, napi_set_named_property(env, res, "message", m));
+  NAPI_CALL(env, napi_create_double(env, (double)r.n_bad, &v));
+  NAPI_CALL(env, napi_set_named_property(env, res, "nBad", v));
+  NAPI_CALL(env, napi_create_double(env, (double)r.first_bad, &v));
+  NAPI_CALL(env, napi_set_named_property(env, res, "firstBad", v));
+  NAPI_CALL(env, napi_create_double(env, (double)r.n_constraints, &v));
+  NAPI_CALL(env, napi_set_named_property(env, res, "nConstraints", v));
+  NAPI_CALL(env, napi_create_array_with_length(env, r.n_listed, &bad));
+  for (uint32_t k = 0; k < r.n_listed && k < 16; ++k) {
+    NAPI_CALL(env, napi_create_double(env, (double)r.bad[k], &v));
+    NAPI_CALL(env, napi_set_element(env, bad, k, v));
+  }
+  NAPI_CALL(env, napi_set_named_property(env, res, "bad", bad));
+  return res;
 }
 
 /* a JS string argument into buf (NULL when absent / undefined / not a string) */
@@ -869,6 +916,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauChallengeContribute", NULL, js_ptau_challenge_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"ptauImportResponse", NULL, js_ptau_import_response, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromR1cs", NULL, js_zkey_verify_r1cs, NULL, NULL, NULL, napi_default, NULL},
+      {"wtnsCheck", NULL, js_wtns_check, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

@@ -57,6 +57,17 @@ class _Proof(ctypes.Structure):
     ]
 
 
+class _CheckResult(ctypes.Structure):  # zkp_check_result
+    _fields_ = [
+        ("valid", ctypes.c_int),
+        ("n_bad", ctypes.c_uint64),
+        ("first_bad", ctypes.c_uint64),
+        ("n_constraints", ctypes.c_uint64),
+        ("n_listed", ctypes.c_uint32),
+        ("bad", ctypes.c_uint64 * 16),
+    ]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -194,6 +205,21 @@ def load_library(path: str = LIB_PATH):
             for name in ("zkp_ptau_export_challenge", "zkp_ptau_challenge_contribute", "zkp_ptau_import_response",
                          "zkp_ptau_challenge_timings", "zkp_points_decompress", "zkp_points_from_uncompressed",
                          "zkp_field_sqrt"):
+                getattr(lib, name).restype = ctypes.c_int
+        if hasattr(lib, "zkp_wtns_check"):  # wtns check
+            rp = ctypes.POINTER(_CheckResult)
+            u32p = ctypes.POINTER(ctypes.c_uint32)
+            lib.zkp_checker_load.argtypes = [ctypes.c_int, u8p, sz, ctypes.POINTER(P)]
+            lib.zkp_checker_info.argtypes = [P, u32p, u32p, u32p, ctypes.POINTER(ctypes.c_uint64)]
+            lib.zkp_checker_paths.argtypes = [P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
+            lib.zkp_checker_check.argtypes = [P, u8p, sz, rp, ctypes.c_char_p, sz]
+            lib.zkp_checker_check_staged.argtypes = [P, P, ctypes.c_int, ctypes.c_int, rp, ctypes.c_char_p, sz]
+            lib.zkp_checker_free.argtypes = [P]
+            lib.zkp_checker_free.restype = None
+            lib.zkp_wtns_check.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, rp, ctypes.c_char_p, sz]
+            lib.zkp_wtns_check_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+            for name in ("zkp_checker_load", "zkp_checker_info", "zkp_checker_paths", "zkp_checker_check",
+                         "zkp_checker_check_staged", "zkp_wtns_check", "zkp_wtns_check_timings"):
                 getattr(lib, name).restype = ctypes.c_int
         for name in ("zkp_zkey_verify_frominit", "zkp_zkey_verify", "zkp_zkey_verify_timings", "zkp_rlc_coeffs",
                      "zkp_points_check", "zkp_rlc_g1", "zkp_ptau_verify", "zkp_ptau_verify_sections", "zkp_ptau_verify_timings",
@@ -766,6 +792,96 @@ def zkey_verify_timings() -> dict:
     keys = ["total", "host_transcript_pairings", "section_compares", "upload", "point_check", "coeff_gen", "plan",
             "accumulate_init", "accumulate_key", "host_fold", "lincomb_wall", "chunks"]
     return dict(zip(keys, list(out)))
+
+
+class CheckResult:
+    """The verdict of a witness check: valid, message ("OK" or "INVALID: ..."), n_bad (the exact number of
+    failing constraints), first_bad (the lowest; None if none), bad (the lowest min(16, n_bad), ascending),
+    n_constraints.  Truthy when the witness satisfies the circuit."""
+
+    def __init__(self, res: _CheckResult, message: str):
+        self.valid = bool(res.valid)
+        self.message = message
+        self.n_bad = int(res.n_bad)
+        self.bad = [int(res.bad[k]) for k in range(min(int(res.n_listed), 16))]
+        self.first_bad = int(res.first_bad) if self.n_bad else None
+        self.n_constraints = int(res.n_constraints)
+
+    def __bool__(self):
+        return self.valid
+
+    def __repr__(self):
+        return "CheckResult(valid=%r, message=%r, n_bad=%d, bad=%r)" % (self.valid, self.message, self.n_bad, self.bad)
+
+
+class WitnessChecker:
+    """A circuit's A, B and C matrices (a circom .r1cs) resident on one device: `wtns check` of any number
+    of witnesses against it.  A malformed r1cs raises ZkpError before any device work."""
+
+    def __init__(self, r1cs, device: int = 0):
+        lib = load_library()
+        if not isinstance(r1cs, (bytes, bytearray, memoryview)) and not hasattr(r1cs, "ptr"):
+            r1cs = open(r1cs, "rb").read()
+        rp, rlen, rk = _in(r1cs)
+        h = ctypes.c_void_p()
+        _check(lib.zkp_checker_load(device, rp, rlen, ctypes.byref(h)))
+        self._h = h
+        self.device = device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().zkp_checker_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        nv, npub, nc = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        nt = ctypes.c_uint64()
+        lib = load_library()
+        _check(lib.zkp_checker_info(self._h, ctypes.byref(nv), ctypes.byref(npub), ctypes.byref(nc), ctypes.byref(nt)))
+        paths = (ctypes.c_uint64 * 2)()
+        _check(lib.zkp_checker_paths(self._h, paths, 2))
+        return {"n_vars": nv.value, "n_public": npub.value, "n_constraints": nc.value, "n_terms": nt.value,
+                "n_long": int(paths[0]), "long_terms": int(paths[1])}
+
+    def check(self, wtns) -> CheckResult:
+        """A .wtns file's bytes against the circuit.  A malformed file or one of another length raises
+        ZkpError; a witness that fails is a verdict, not an error."""
+        wp, wlen, wk = _in(wtns)
+        res = _CheckResult()
+        msg = ctypes.create_string_buffer(VERIFY_MSG_CAP)
+        _check(load_library().zkp_checker_check(self._h, wp, wlen, ctypes.byref(res), msg, VERIFY_MSG_CAP))
+        return CheckResult(res, msg.value.decode())
+
+    def check_staged(self, prover: "Prover", slot: int, dev_index: int = 0) -> CheckResult:
+        """The witness prover.stage() left in `slot`, read in place: stage -> check -> prove_staged."""
+        res = _CheckResult()
+        msg = ctypes.create_string_buffer(VERIFY_MSG_CAP)
+        _check(load_library().zkp_checker_check_staged(self._h, prover._h, dev_index, slot, ctypes.byref(res), msg,
+                                                       VERIFY_MSG_CAP))
+        return CheckResult(res, msg.value.decode())
+
+
+def wtns_check(r1cs, wtns, device: int = 0) -> CheckResult:
+    """`wtns check <circuit.r1cs> <witness.wtns>` in one call (zkp_wtns_check: load, check, free)."""
+    rp, rlen, rk = _in(r1cs)
+    wp, wlen, wk = _in(wtns)
+    res = _CheckResult()
+    msg = ctypes.create_string_buffer(VERIFY_MSG_CAP)
+    _check(load_library().zkp_wtns_check(device, rp, rlen, wp, wlen, ctypes.byref(res), msg, VERIFY_MSG_CAP))
+    return CheckResult(res, msg.value.decode())
+
+
+def wtns_check_timings() -> dict:
+    """ms of the calling thread's last wtns_check / WitnessChecker call (zkp_wtns_check_timings)."""
+    out = (ctypes.c_double * 5)()
+    _check(load_library().zkp_wtns_check_timings(out, 5))
+    return dict(zip(["parse_csr", "upload_convert", "witness_copy", "kernels", "total"], list(out)))
 
 
 def rlc_coeffs(seed: bytes, first_index: int, n: int, device: int = 0):
