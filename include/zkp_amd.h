@@ -218,6 +218,12 @@ zkp_status zkp_ptau_verify_timings(double* ms, int n);
  * The status reports only malformed input (ZKP_ERR_FORMAT, ...) or a device error.  A key that fails
  * a check is ZKP_OK with *valid = 0 and the failing check in msg ("OK" and *valid = 1 otherwise); msg
  * (may be NULL) receives at most msg_cap - 1 characters and a NUL.
+ * The H check accepts a key written by zkp_zkey_import_bellman, as snarkjs does: such a key's section 9
+ * differs from a direct contribution's by a multiple of (w^j)_j (n = 2^p the domain, w = Fr.w[p]), a direction
+ * in which no prover's sum over H has a component.  Points 0..n-2 take the stream's coefficients r_j as before
+ * (indices nL..nL+n-2) and point n - 1 takes r' = -w sum_(j<n-1) r_j w^j mod r, so that sum_j r_j w^j = 0 and the
+ * combination does not see that direction; a wrong H section still passes with probability <= 2^-128 unless it
+ * differs from the right one by such a multiple.  Every key accepted before is accepted, with the same messages.
  * seed32 seeds the linear combinations' coefficients (128-bit: a wrong section passes with
  * probability <= 2^-128 each).  PRODUCTION MUST PASS NULL (32 bytes from the OS CSPRNG): the
  * coefficients must be unpredictable to whoever wrote the key.  Non-NULL is for reproducible tests.
@@ -361,6 +367,9 @@ zkp_status zkp_rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_inde
  * order in and out; out: n points.  For P_j = tau^j G this is L_c(tau) G.  Every exceptional addition
  * (infinity, equal and opposite operands) is computed, not assumed away. */
 zkp_status zkp_group_ifft(int device, int g2, const uint8_t* points, int log_n, uint8_t* out);
+/* The forward direction of the same kernels: out_c = sum_j w^(c j) P_j, no n^-1 (zkp_zkey_export_bellman takes
+ * section 9 through it).  zkp_group_ifft(zkp_group_fft(x)) = x. */
+zkp_status zkp_group_fft(int device, int g2, const uint8_t* points, int log_n, uint8_t* out);
 zkp_status zkp_points_check(int device, int g2, const uint8_t* points, size_t n, uint64_t* n_bad, uint64_t* first_bad);
 zkp_status zkp_rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* points_a,
                       const uint8_t* points_b, size_t n, uint8_t* out_a64, int* inf_a, uint8_t* out_b64, int* inf_b);
@@ -552,6 +561,59 @@ zkp_status zkp_points_decompress(int device, int g2, const uint8_t* compressed, 
 zkp_status zkp_points_from_uncompressed(int device, int g2, const uint8_t* bytes, size_t n, uint8_t* out_lem, uint64_t* n_bad,
                                         uint64_t* first_bad);
 zkp_status zkp_field_sqrt(int device, int fq2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* is_square);
+
+/* ---- The third-party path of phase 2: `snarkjs zkey export bellman | zkey bellman contribute | zkey import
+ * bellman`: a contributor works on an MPCParams file, which the Rust phase2 tools also read, and never holds the
+ * .zkey.  Formats restated from snarkjs 0.4.22 (parity unpinned); tests/helpers/bellman_model.py fixes them byte
+ * for byte.  Every integer is a big-endian u32, every point uncompressed (big-endian standard form, x then y, G2
+ * c1 before c0; 0x40 then zeros: infinity):
+ *   alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2                    G1 G1 G2 G2 G1 G2
+ *   u32 nPublic + 1 | IC        u32 n - 1 | B_0 .. B_(n-2)        u32 nVars - nPublic - 1 | L
+ *   u32 nVars | A               u32 nVars | B1                     u32 nVars | B2 (G2)
+ *   csHash (64)                 u32 nContributions | deltaAfter | g1_s | g1_sx | g2_spx | transcript (384 each)
+ * Up to csHash this is the byte string whose Blake2b-512 zkp_zkey_new records as csHash.  B_i = delta^-1 tau^i
+ * (tau^n - 1) G1, n = 2^p the key's domain.  With w = Fr.w[p], w2 = Fr.w[p + 1] and section 9 holding H_j, the
+ * Lagrange points of the 2n-domain at its odd nodes,
+ *   export:  B_i  = -2 w2^i sum_j w^(ij) H_j, i < n - 1      (zkp_group_fft, then point i times -2 w2^i)
+ *   import:  H'_j = n^-1 sum_i w^(-ij) (-1/2 w2^-i) B_i       (B_(n-1) := infinity; scaling, zkp_group_ifft)
+ * H' is NOT byte-equal to the section 9 a direct zkp_zkey_contribute_entropy writes: the two differ by a multiple
+ * of (w^j)_j, which no prover notices and zkp_zkey_verify accepts (above).  Every per-point pass (decode, point
+ * check, scaling, encode) streams through the device in chunks of ZKP_PTAU_CHUNK points.
+ *
+ * zkp_mpcparams_info: host only.  Parses the layout: the counts against the length, n - 1 = 2^p - 1 with
+ * p <= 27, the counts of L, A, B1, B2 and IC against each other, no trailing bytes; ZKP_ERR_FORMAT
+ * "mpcparams: ..." otherwise.
+ *
+ * zkp_zkey_export_bellman: the key is parsed, header and section 10 included, and anything malformed refused
+ * with ZKP_ERR_FORMAT before the device is touched.
+ *
+ * zkp_zkey_bellman_contribute: the secret k and its proof of knowledge are drawn exactly as by
+ * zkp_zkey_contribute_entropy (same rng, same order; the transcript over csHash and the earlier contributions).
+ * delta1 and delta2 become k times their old values, every H and L point is multiplied by k^-1, every other
+ * section is copied, the new 384-byte contribution is appended and its Blake2b-512 written to hash64 (may be
+ * NULL).  Every point must be canonical and on its curve, else ZKP_ERR_FORMAT "mpcparams: <section name> point
+ * <i> is not on the curve" (checked on the device; the smallest i of the first such section).
+ *
+ * zkp_zkey_import_bellman: the response must have the old key's counts and csHash, exactly one contribution
+ * more than the old key, its earlier contributions, alpha1, beta1, beta2, gamma2, IC, A, B1 and B2 equal to the
+ * old key's, delta1 equal to the new contribution's deltaAfter, and every point canonical and on its curve;
+ * each failure is ZKP_ERR_FORMAT "mpcparams: ..." naming the section.  Output: the old key's sections 1 and
+ * 3-7 unchanged, section 2 with the new deltas, section 8 the decoded L, section 9 = H', section 10 with a
+ * type-0 record appended (name: recorded unless NULL; the old records keep theirs).  The contribution's
+ * same-ratio checks are NOT run here: zkp_zkey_verify does that on the result, as in snarkjs.
+ *
+ * zkp_zkey_bellman_timings: ms of the calling thread's last call of the three: [0] total, [1] parse and other
+ * host work, [2] upload, [3] decoding, [4] point check, [5] scaling by k^-1, [6] the forward / inverse
+ * transform, [7] coset scaling, [8] encoding, [9] download, [10] chunks. */
+zkp_status zkp_mpcparams_info(const uint8_t* buf, size_t len, uint32_t* n_public, uint32_t* domain_size, uint32_t* n_vars,
+                              uint32_t* n_contributions);
+zkp_status zkp_zkey_export_bellman(int device, const uint8_t* zkey, size_t len, uint8_t** out, size_t* out_len);
+zkp_status zkp_zkey_bellman_contribute(int device, const uint8_t* challenge, size_t len,
+                                       const uint8_t* rand64 /* NULL: OS CSPRNG */, const char* entropy, uint8_t** out,
+                                       size_t* out_len, uint8_t* hash64 /* may be NULL */);
+zkp_status zkp_zkey_import_bellman(int device, const uint8_t* old_zkey, size_t len, const uint8_t* response,
+                                   size_t response_len, const char* name, uint8_t** out, size_t* out_len);
+zkp_status zkp_zkey_bellman_timings(double* ms, int n);
 
 /* `wtns check <circuit.r1cs> <witness.wtns>`: does the witness satisfy every constraint A.w * B.w = C.w of
  * the circuit, and if not, which ones fail.  Later snarkjs versions ship this command and circom_tester's

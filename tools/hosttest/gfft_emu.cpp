@@ -1,11 +1,12 @@
-// CPU replay of the group inverse FFT (gfft_kernels.hpp per-thread bodies, the launches of
+// CPU replay of the group FFT (gfft_kernels.hpp per-thread bodies, the launches of
 // ptau_prepare.hip in the device's stage order) for checking it without a GPU.
-// usage: gfft_emu <g1|g2> <file of 2^log_n zkey-layout points> <log_n> [--events] [--window 1|2]
+// usage: gfft_emu <g1|g2> <file of 2^log_n zkey-layout points> <log_n> [--events] [--window 1|2] [--forward]
 //   -> one line per output point, natural order: the affine coordinates (decimal) or `inf`
 //   --events: after them a `geometry` line and one `event <stage> <dbl> <cancel> <acc_inf> <q_inf>` line
 //     per stage: how often the additions of that stage took an exceptional branch (curve.hpp
 //     ZKP_XYZZ_EVENT), the additions inside the scalar multiplications included
 //   --window W: the scalar multiplications' window bits (gfft::scale; default 2, as the device)
+//   --forward: out_c = sum_j w^(c j) P_j (group_fft) instead of the inverse transform
 // A level of at most Geom::TILE points is one workgroup: load, every stage on the tile, finish.  A larger
 // one runs the first Geom::LG stages tile by tile, the remaining stages over the whole vector, one
 // launch each, then the finish launch.
@@ -35,7 +36,7 @@ static inline void emu_event(int kind) { ++g_events[g_stage][kind]; }
 using namespace zkp;
 
 template <class F, int WB>
-static std::vector<uint32_t> run(const std::vector<uint32_t>& in, int p) {
+static std::vector<uint32_t> run(const std::vector<uint32_t>& in, int p, bool fwd) {
   using G = gfft::Geom<F>;
   constexpr int W = G::W;
   const size_t n = (size_t)1 << p;
@@ -50,13 +51,13 @@ static std::vector<uint32_t> run(const std::vector<uint32_t>& in, int p) {
     for (size_t q = 0; q < cnt; ++q) store_xyzz(lds.data(), q, gfft::load_point<F>(in.data(), gfft::brev(tile * cnt + q, p)));
     for (int s = 0; s < l; ++s) {
       set_stage("stage." + std::to_string(s));
-      for (size_t i = 0; i < cnt / 2; ++i) gfft::stage<F, WB>(lds.data(), tw.data(), p, s, i);
+      for (size_t i = 0; i < cnt / 2; ++i) gfft::stage<F, WB>(lds.data(), tw.data(), p, s, i, fwd);
     }
     for (size_t q = 0; q < cnt; ++q) store_xyzz(work.data(), tile * cnt + q, load_xyzz<F>(lds.data(), q));
   }
   for (int s = l; s < p; ++s) {
     set_stage("stage." + std::to_string(s));
-    for (size_t i = 0; i < n / 2; ++i) gfft::stage<F, WB>(work.data(), tw.data(), p, s, i);
+    for (size_t i = 0; i < n / 2; ++i) gfft::stage<F, WB>(work.data(), tw.data(), p, s, i, fwd);
   }
   set_stage("finish");
   for (size_t i = 0; i < n; ++i) gfft::finish<F>(load_xyzz<F>(work.data(), i), tw.data(), out.data(), i);
@@ -71,15 +72,16 @@ static std::string dec(const uint32_t* w) {  // a zkey-layout coordinate (Montgo
 
 int main(int argc, char** argv) {
   std::vector<const char*> pos;
-  bool events = false;
+  bool events = false, fwd = false;
   int window = 2;
   for (int i = 1; i < argc; ++i) {
     if (!strcmp(argv[i], "--events")) events = true;
+    else if (!strcmp(argv[i], "--forward")) fwd = true;
     else if (!strcmp(argv[i], "--window") && i + 1 < argc) window = atoi(argv[++i]);
     else pos.push_back(argv[i]);
   }
   if (pos.size() != 3 || (window != 1 && window != 2)) {
-    fprintf(stderr, "usage: gfft_emu <g1|g2> <file> <log_n> [--events] [--window 1|2]\n");
+    fprintf(stderr, "usage: gfft_emu <g1|g2> <file> <log_n> [--events] [--window 1|2] [--forward]\n");
     return 2;
   }
   const bool g2 = std::string(pos[0]) == "g2";
@@ -90,8 +92,8 @@ int main(int argc, char** argv) {
   FILE* f = fopen(pos[1], "rb");
   if (!f || fread(in.data(), 4, in.size(), f) != in.size()) return 1;
   fclose(f);
-  const std::vector<uint32_t> out = g2 ? (window == 2 ? run<Fq2, 2>(in, p) : run<Fq2, 1>(in, p))
-                                       : (window == 2 ? run<Fq, 2>(in, p) : run<Fq, 1>(in, p));
+  const std::vector<uint32_t> out = g2 ? (window == 2 ? run<Fq2, 2>(in, p, fwd) : run<Fq2, 1>(in, p, fwd))
+                                       : (window == 2 ? run<Fq, 2>(in, p, fwd) : run<Fq, 1>(in, p, fwd));
   for (size_t i = 0; i < n; ++i) {
     const uint32_t* q = out.data() + i * pw;
     bool inf = true;

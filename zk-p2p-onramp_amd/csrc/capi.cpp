@@ -31,6 +31,7 @@
 #include "ptau_contribute.hpp"
 #include "ptau_verify.hpp"
 #include "wtns_check.hpp"
+#include "zkey_bellman.hpp"
 #include "zkey_io.hpp"
 #include "zkey_verify.hpp"
 
@@ -421,6 +422,57 @@ zkp_status zkp_ptau_prepare_timings(double* ms, int n) {
 zkp_status zkp_group_ifft(int device, int g2, const uint8_t* points, int log_n, uint8_t* out) {
   if (!points || !out) return fail(ZKP_ERR_INVALID_ARG, "null argument");
   return guard([&] { zkp::group_ifft(device, g2 != 0, points, log_n, out); });
+}
+
+zkp_status zkp_group_fft(int device, int g2, const uint8_t* points, int log_n, uint8_t* out) {
+  if (!points || !out) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::group_fft(device, g2 != 0, points, log_n, out); });
+}
+
+zkp_status zkp_mpcparams_info(const uint8_t* buf, size_t len, uint32_t* n_public, uint32_t* domain_size, uint32_t* n_vars,
+                              uint32_t* n_contributions) {
+  if (!buf || !n_public || !domain_size || !n_vars || !n_contributions) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] {
+    const zkp::MpcParamsFile f = zkp::mpcparams_parse(buf, len);
+    *n_public = f.n_public, *domain_size = f.domain_size, *n_vars = f.n_vars, *n_contributions = f.n_contributions;
+  });
+}
+
+zkp_status zkp_zkey_export_bellman(int device, const uint8_t* zkey, size_t len, uint8_t** out, size_t* out_len) {
+  if (!zkey || !len || !out || !out_len) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] { buf = zkp::zkey_export_bellman(device, zkey, len); });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_zkey_bellman_contribute(int device, const uint8_t* challenge, size_t len, const uint8_t* rand64,
+                                       const char* entropy, uint8_t** out, size_t* out_len, uint8_t* hash64) {
+  if (!challenge || !len || !entropy || !out || !out_len) return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] {
+    (void)zkp::mpcparams_parse(challenge, len);  // a malformed file is refused before the OS is asked for randomness
+    zkp::ChaChaRng rng = entropy_rng(rand64, entropy);
+    buf = zkp::zkey_bellman_contribute(device, challenge, len, rng, hash64);
+  });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_zkey_import_bellman(int device, const uint8_t* old_zkey, size_t len, const uint8_t* response,
+                                   size_t response_len, const char* name, uint8_t** out, size_t* out_len) {
+  if (!old_zkey || !len || !response || !response_len || !out || !out_len)
+    return fail(ZKP_ERR_INVALID_ARG, "null argument or zero length");
+  std::vector<uint8_t> buf;
+  zkp_status s = guard([&] { buf = zkp::zkey_import_bellman(device, old_zkey, len, response, response_len, name); });
+  return s != ZKP_OK ? s : hand_out(std::move(buf), out, out_len);
+}
+
+zkp_status zkp_zkey_bellman_timings(double* ms, int n) {
+  if (!ms || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const zkp::BellmanTimings t = zkp::zkey_bellman_timings();
+  const double v[11] = {t.total_ms,     t.parse_ms, t.upload_ms, t.decode_ms,   t.check_ms,        t.scale_ms,
+                        t.transform_ms, t.coset_ms, t.encode_ms, t.download_ms, (double)t.chunks};
+  for (int i = 0; i < n && i < 11; ++i) ms[i] = v[i];
+  return ZKP_OK;
 }
 
 zkp_status zkp_rlc_coeffs(int device, const uint8_t* seed32, uint64_t first_index, size_t n, uint8_t* out) {

@@ -1,7 +1,9 @@
-// Per-thread bodies of the group inverse FFT (ptau_prepare.hip): __host__ __device__ so that
+// Per-thread bodies of the group FFT (ptau_prepare.hip), both directions: __host__ __device__ so that
 // tools/hosttest/gfft_emu.cpp can replay the launches on the CPU.
 //
-//   out_c = n^-1 * sum_j w^(-c j) * P_j,   n = 2^p, w = Fr.w[p]   (natural order in and out)
+//   inverse:  out_c = n^-1 * sum_j w^(-c j) * P_j,   n = 2^p, w = Fr.w[p]   (natural order in and out)
+//   forward:  out_c =        sum_j w^(+c j) * P_j    (the same schedule with the twiddles w_(2m)^+k and no
+//             n^-1 stage; `zkey export bellman`, zkey_bellman.hip, takes section 9 through it)
 //
 // Radix-2 decimation in time over XYZZ points: the loads read the input in bit-reversed order, stage
 // s < p (half-length m = 2^s) pairs positions lo = (i >> s << s + 1) | k and lo + m, k = i mod m, with
@@ -13,7 +15,7 @@
 // every level: entry i < 28 is w_28^-(2^i), so w_(2m)^-(2^j) = entry[j + 27 - s] whatever the level,
 // and a thread multiplies the entries of k's set bits (at most 27 Fr products beside the ~380 group
 // operations of its butterfly); entry 28 + p is 2^-p; entry 57 is 2^256 mod q, the factor from the
-// device's Montgomery form to the zkey's.
+// device's Montgomery form to the zkey's; entries 58 + i, i < 28, are w_28^+(2^i), the forward direction's.
 #pragma once
 #include "curve.hpp"
 
@@ -23,7 +25,8 @@ namespace gfft {
 constexpr int TW_ROOT = 28;                    // the table's root of unity: Fr.w[28]
 constexpr int TW_NINV = TW_ROOT;               // entry TW_NINV + p = 2^-p, p <= 28
 constexpr int TW_TO_ZKEY = TW_ROOT + 29;       // 2^256 mod q
-constexpr int TW_ENTRIES = TW_TO_ZKEY + 1;
+constexpr int TW_FWD = TW_TO_ZKEY + 1;          // entry TW_FWD + i = w_28^(2^i), i < 28
+constexpr int TW_ENTRIES = TW_FWD + TW_ROOT;
 constexpr int MAX_LOG_N = TW_ROOT;
 
 // Points of one level that one workgroup transforms in LDS (64 KB of XYZZ points: 512 G1, 256 G2),
@@ -60,12 +63,15 @@ ZDEV Fr tw_entry(const uint32_t* tw, int e) { return to_mont(load_fe<FrCfg>(tw +
 ZDEV void fr_words(const Fr& a_mont, uint32_t (&w)[8]) { pack(from_mont(a_mont), w); }
 
 // The scalars of butterfly k of stage s of level p, standard form: b takes tb, and a takes ta where
-// scale_a (the last stage: ta = 2^-p, tb = 2^-p w_(2m)^-k); elsewhere tb = w_(2m)^-k.
-ZDEV void twiddles(const uint32_t* tw, int p, int s, size_t k, uint32_t (&ta)[8], uint32_t (&tb)[8], bool& scale_a) {
+// scale_a (the last stage: ta = 2^-p, tb = 2^-p w_(2m)^-k); elsewhere tb = w_(2m)^-k.  fwd: tb = w_(2m)^+k
+// in every stage, and no stage scales a.
+ZDEV void twiddles(const uint32_t* tw, int p, int s, size_t k, uint32_t (&ta)[8], uint32_t (&tb)[8], bool& scale_a,
+                   bool fwd = false) {
   Fr t = fe_one<FrCfg>();
+  const int root = fwd ? TW_FWD : 0;
   for (int j = 0; j < s; ++j)
-    if ((k >> j) & 1) t = mul(t, tw_entry(tw, j + TW_ROOT - 1 - s));
-  scale_a = s == p - 1;
+    if ((k >> j) & 1) t = mul(t, tw_entry(tw, root + j + TW_ROOT - 1 - s));
+  scale_a = !fwd && s == p - 1;
   if (scale_a) {
     const Fr ninv = tw_entry(tw, TW_NINV + p);
     t = mul(t, ninv);
@@ -86,10 +92,12 @@ inline void fill_table(uint32_t* tw) {
   };
   uint32_t rw[8];
   for (int i = 0; i < 8; ++i) rw[i] = FR_ROOTS_W[TW_ROOT][i];
-  Fr g = inv(to_mont(unpack<FrCfg>(rw)));
+  Fr f = to_mont(unpack<FrCfg>(rw)), g = inv(f);
   for (int i = 0; i < TW_ROOT; ++i) {
     put(i, g);
+    put(TW_FWD + i, f);
     g = mul(g, g);
+    f = mul(f, f);
   }
   const uint32_t two[8] = {2, 0, 0, 0, 0, 0, 0, 0};
   const Fr half = inv(to_mont(unpack<FrCfg>(two)));
@@ -214,15 +222,15 @@ ZDEV Xyzz<F> load_point(const uint32_t* in, size_t idx) {
 
 // butterfly i of stage s of level p on the XYZZ points at buf: a workgroup's tile in LDS (i counts
 // inside the tile; the twiddle depends on i mod 2^s only, so it is the same in every tile) or the
-// level's vector in HBM
+// level's vector in HBM.  fwd: the forward transform's stage (twiddles)
 template <class F, int WB>
-ZDEV void stage(uint32_t* buf, const uint32_t* tw, int p, int s, size_t i) {
+ZDEV void stage(uint32_t* buf, const uint32_t* tw, int p, int s, size_t i, bool fwd = false) {
   size_t lo, k;
   pair_of(s, i, lo, k);
   const size_t hi = lo + ((size_t)1 << s);
   uint32_t ta[8], tb[8];
   bool scale_a;
-  twiddles(tw, p, s, k, ta, tb, scale_a);
+  twiddles(tw, p, s, k, ta, tb, scale_a, fwd);
   Xyzz<F> a = load_xyzz<F>(buf, lo), b = load_xyzz<F>(buf, hi);
   butterfly<WB>(a, b, ta, tb, scale_a);
   store_xyzz(buf, lo, a);

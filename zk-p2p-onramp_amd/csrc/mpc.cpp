@@ -13,6 +13,7 @@
 #include "ptau_contribute.hpp"
 #include "ptau_verify.hpp"
 #include "spans.hpp"
+#include "zkey_bellman.hpp"
 #include "zkey_verify.hpp"
 
 namespace zkp {
@@ -498,6 +499,13 @@ static std::string mpc_name_utf8(const std::string& name) {
   return out;
 }
 
+std::vector<uint8_t> mpc_name_params(const std::string& name) {
+  const std::string nm = mpc_name_utf8(name);
+  std::vector<uint8_t> prm{1, (uint8_t)nm.size()};
+  prm.insert(prm.end(), nm.begin(), nm.end());
+  return prm;
+}
+
 void mpc_contribute(MpcParams& m, ChaChaRng& rng, const Affine<HFq>& delta1_before, uint32_t type,
                     const std::string& name, const uint8_t* beacon, size_t beacon_len, uint32_t num_iterations_exp,
                     uint8_t k32[32]) {
@@ -516,12 +524,7 @@ void mpc_contribute(MpcParams& m, ChaChaRng& rng, const Affine<HFq>& delta1_befo
   c.g2_spx = g2_times(hash_to_g2(c.transcript), k);
   c.delta_after = g1_times(delta1_before, k);
   c.type = type;
-  if (!name.empty()) {
-    const std::string nm = mpc_name_utf8(name);
-    c.params.push_back(1);
-    c.params.push_back((uint8_t)nm.size());
-    c.params.insert(c.params.end(), nm.begin(), nm.end());
-  }
+  if (!name.empty()) c.params = mpc_name_params(name);
   if (type == 1) {
     if (beacon_len > 255 || num_iterations_exp > 255) throw ZkpError(ZKP_ERR_INVALID_ARG, "beacon: parameter too long");
     c.params.push_back(2);  // numIterationsExp: the id, then its one value byte (no length byte)
@@ -797,7 +800,8 @@ bool zkey_verify_frominit(int device, const uint8_t* init, size_t init_len, cons
     const std::string name = id == 8 ? "L" : "H";
     if (s[id].len != s0[id].len) return bad("INVALID: " + name + " section size");
     const size_t count = s[id].len / 64;
-    const RlcResult r = rlc_g1(device, seed, first_index, s0[id].ptr, s[id].ptr, count);
+    // H: the last coefficient closes sum_j r_j w^j = 0, so that an imported key's section passes (zkey_verify.hpp)
+    const RlcResult r = rlc_g1(device, seed, first_index, s0[id].ptr, s[id].ptr, count, id == 9);
     first_index += count;
     tm.rlc.add(r.t);
     if (r.first_bad_b != RLC_NO_BAD)
@@ -1262,5 +1266,105 @@ std::vector<uint8_t> ptau_record_of_key(const uint8_t key_lem[768], const uint8_
   rec.insert(rec.end(), prm.begin(), prm.end());
   return rec;
 }
+
+// ---------------------------------------------------------------- the MPCParams file (zkey_bellman.hpp)
+namespace {
+
+uint32_t rd32be(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3]; }
+
+}  // namespace
+
+MpcParamsFile mpcparams_parse(const uint8_t* buf, size_t len) {
+  MpcParamsFile f;
+  size_t o = 0;
+  auto need = [&](uint64_t bytes, const char* what) {
+    if ((uint64_t)(len - o) < bytes) throw ZkpError(ZKP_ERR_FORMAT, std::string("mpcparams: the file ends inside ") + what);
+  };
+  // a counted section of `pb`-byte points: -> its first point, the count in *count
+  auto section = [&](const char* what, size_t pb, size_t* count) {
+    need(4, what);
+    *count = rd32be(buf + o);
+    o += 4;
+    need((uint64_t)*count * pb, what);
+    const uint8_t* p = buf + o;
+    o += *count * pb;
+    return p;
+  };
+  need(MPCPARAMS_HEADER, "the header");
+  f.header = buf;
+  o = MPCPARAMS_HEADER;
+  size_t n_a = 0, n_b1 = 0, n_b2 = 0;
+  f.ic = section("IC", 64, &f.n_ic);
+  f.h = section("H", 64, &f.n_h);
+  f.l = section("L", 64, &f.n_l);
+  f.a = section("A", 64, &n_a);
+  f.b1 = section("B1", 64, &n_b1);
+  f.b2 = section("B2", 128, &n_b2);
+  if (!f.n_ic) throw ZkpError(ZKP_ERR_FORMAT, "mpcparams: IC has no point");
+  const uint64_t n = (uint64_t)f.n_h + 1;
+  if ((n & (n - 1)) || n > (uint64_t(1) << 27))
+    throw ZkpError(ZKP_ERR_FORMAT, "mpcparams: H has " + std::to_string(f.n_h) + " points, which is not 2^p - 1 with p <= 27");
+  if (n_b1 != n_a || n_b2 != n_a) throw ZkpError(ZKP_ERR_FORMAT, "mpcparams: A, B1 and B2 differ in their point counts");
+  if (n_a < f.n_ic || f.n_l != n_a - f.n_ic)
+    throw ZkpError(ZKP_ERR_FORMAT, "mpcparams: L has " + std::to_string(f.n_l) + " points where A and IC want " +
+                                       std::to_string((long long)n_a - (long long)f.n_ic));
+  f.n_public = (uint32_t)(f.n_ic - 1), f.n_vars = (uint32_t)n_a, f.domain_size = (uint32_t)n;
+  while ((uint64_t(1) << f.log_domain) < n) ++f.log_domain;
+  need(64, "csHash");
+  f.cs_hash = buf + o;
+  o += 64;
+  size_t nc = 0;
+  f.contributions = section("the contributions", MPCPARAMS_CONTRIBUTION, &nc);
+  f.n_contributions = (uint32_t)nc;
+  if (o != len) throw ZkpError(ZKP_ERR_FORMAT, "mpcparams: " + std::to_string(len - o) + " trailing bytes");
+  return f;
+}
+
+void mpcparams_header(const Affine<HFq>& alpha1, const Affine<HFq>& beta1, const Affine<HFq2>& beta2,
+                      const Affine<HFq2>& gamma2, const Affine<HFq>& delta1, const Affine<HFq2>& delta2,
+                      uint8_t out[MPCPARAMS_HEADER]) {
+  g1_u(alpha1, out), g1_u(beta1, out + 64), g2_u(beta2, out + 128), g2_u(gamma2, out + 256);
+  g1_u(delta1, out + MPCPARAMS_DELTA1_AT), g2_u(delta2, out + MPCPARAMS_DELTA2_AT);
+}
+
+void mpcparams_put_contribution(const MpcContribution& c, uint8_t out[MPCPARAMS_CONTRIBUTION]) {
+  g1_u(c.delta_after, out), g1_u(c.g1_s, out + 64), g1_u(c.g1_sx, out + 128), g2_u(c.g2_spx, out + 192);
+  std::memcpy(out + 320, c.transcript, 64);
+}
+
+Affine<HFq> mpcparams_g1(const uint8_t in[64], const std::string& what) {
+  Affine<HFq> a{HFq::zero(), HFq::zero(), false};
+  const bool ok = inf_from_u(in, 64, a.inf) && (a.inf || (fq_from_be(in, a.x) && fq_from_be(in + 32, a.y) && host::g1_on_curve(a)));
+  if (!ok) throw ZkpError(ZKP_ERR_FORMAT, "mpcparams: " + what + " is not on the curve");
+  return a;
+}
+
+Affine<HFq2> mpcparams_g2(const uint8_t in[128], const std::string& what) {
+  Affine<HFq2> a{HFq2::zero(), HFq2::zero(), false};
+  const bool ok = inf_from_u(in, 128, a.inf) &&
+                  (a.inf || (fq_from_be(in, a.x.c1) && fq_from_be(in + 32, a.x.c0) && fq_from_be(in + 64, a.y.c1) &&
+                             fq_from_be(in + 96, a.y.c0) && host::g2_on_curve(a)));
+  if (!ok) throw ZkpError(ZKP_ERR_FORMAT, "mpcparams: " + what + " is not on the curve");
+  return a;
+}
+
+MpcParams mpcparams_read_mpc(const MpcParamsFile& f) {
+  MpcParams m;
+  std::memcpy(m.cs_hash, f.cs_hash, 64);
+  for (uint32_t i = 0; i < f.n_contributions; ++i) {
+    const uint8_t* p = f.contributions + (size_t)i * MPCPARAMS_CONTRIBUTION;
+    const std::string what = "contribution " + std::to_string(i);
+    MpcContribution c;
+    c.delta_after = mpcparams_g1(p, what + " deltaAfter");
+    c.g1_s = mpcparams_g1(p + 64, what + " g1_s");
+    c.g1_sx = mpcparams_g1(p + 128, what + " g1_sx");
+    c.g2_spx = mpcparams_g2(p + 192, what + " g2_spx");
+    std::memcpy(c.transcript, p + 320, 64);
+    m.contributions.push_back(std::move(c));
+  }
+  return m;
+}
+
+Affine<HFq2> mpc_g2_times(const Affine<HFq2>& p, const uint8_t k32[32]) { return g2_times(p, host::u256_from_le(k32)); }
 
 }  // namespace zkp

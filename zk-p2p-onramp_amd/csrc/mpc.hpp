@@ -73,6 +73,9 @@ void mpc_contribute(MpcParams& m, ChaChaRng& rng, const host::Affine<host::Fq>& 
                     const std::string& name, const uint8_t* beacon, size_t beacon_len, uint32_t num_iterations_exp,
                     uint8_t k32[32]);
 
+// the parameter bytes that record a contribution's name (id 1, the length, the name cut as snarkjs cuts it)
+std::vector<uint8_t> mpc_name_params(const std::string& name);
+
 // csHash of a new key (`zkey new`): over its header points and point sections (key bytes, zkey
 // layout) and the H points (tau^(n+i) - tau^i) G1 from the ptau's tauG1 (LEM, >= 2n points)
 void mpc_cs_hash_new(const uint8_t* zkey, size_t len, const uint8_t* tau_g1, size_t tau_g1_points, uint8_t out[64]);

@@ -182,8 +182,10 @@ struct PrepareTimings {
 };
 PrepareTimings ptau_prepare_timings();
 // out_c = n^-1 sum_j w^(-c j) P_j over n = 2^log_n zkey-layout points (w = Fr.w[log_n]), natural order
-// in and out, through the kernels of ptau_prepare_phase2
-void group_ifft(int device, bool g2, const uint8_t* points, int log_n, uint8_t* out);
+// in and out, through the kernels of ptau_prepare_phase2.  kernel_ms (if not null): the launches' device ms
+void group_ifft(int device, bool g2, const uint8_t* points, int log_n, uint8_t* out, double* kernel_ms = nullptr);
+// the forward direction of the same kernels: out_c = sum_j w^(c j) P_j, no n^-1
+void group_fft(int device, bool g2, const uint8_t* points, int log_n, uint8_t* out, double* kernel_ms = nullptr);
 
 // kernel-level helpers (C-ABI zkp_msm_g1/g2, zkp_ntt_fr)
 // c / depth: window bits and base-table depth (0 = automatic, as the prover)

@@ -60,7 +60,8 @@ struct Vecs {
 // blockIdx.y = the vector; work holds the vectors back to back.
 template <class F, int WB>
 __global__ __launch_bounds__(Geom<F>::TPB) void k_gfft_local(Vecs v, uint32_t* __restrict__ work,
-                                                             const uint32_t* __restrict__ tw, int level) {
+                                                             const uint32_t* __restrict__ tw, int level,
+                                                             bool fwd) {
   using G = Geom<F>;
   __shared__ __attribute__((aligned(16))) uint32_t lds[G::LDS_WORDS];
   const int vec = blockIdx.y;
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(Geom<F>::TPB) void k_gfft_local(Vecs v, uint32_t* _
     store_xyzz(lds, q, gfft::load_point<F>(v.in[vec], gfft::brev(tile * cnt + q, p)));
   __syncthreads();
   for (int s = 0; s < l; ++s) {
-    if (threadIdx.x < cnt / 2) gfft::stage<F, WB>(lds, tw, p, s, threadIdx.x);
+    if (threadIdx.x < cnt / 2) gfft::stage<F, WB>(lds, tw, p, s, threadIdx.x, fwd);
     __syncthreads();
   }
   for (size_t q = threadIdx.x; q < cnt; q += G::TPB) {
@@ -88,10 +89,10 @@ __global__ __launch_bounds__(Geom<F>::TPB) void k_gfft_local(Vecs v, uint32_t* _
 // stage s >= LG of level p, in place: one butterfly per thread
 template <class F, int WB>
 __global__ __launch_bounds__(Geom<F>::TPB) void k_gfft_stage(uint32_t* __restrict__ work, const uint32_t* __restrict__ tw,
-                                                             int p, int s) {
+                                                             int p, int s, bool fwd) {
   const size_t n = (size_t)1 << p, i = (size_t)blockIdx.x * Geom<F>::TPB + threadIdx.x;
   if (i >= n / 2) return;
-  gfft::stage<F, WB>(work + (size_t)blockIdx.y * n * 4 * Geom<F>::W, tw, p, s, i);
+  gfft::stage<F, WB>(work + (size_t)blockIdx.y * n * 4 * Geom<F>::W, tw, p, s, i, fwd);
 }
 
 // the level's XYZZ results -> affine, zkey layout, at the level's place in each section
@@ -121,9 +122,9 @@ void run_levels(const Vecs& v, int nvec, int power, uint32_t* work, const uint32
   for (int p = power; p > G::LG; --p) {
     const size_t n = (size_t)1 << p;
     sp.begin(st);
-    hipLaunchKernelGGL((k_gfft_local<F, WB>), dim3((unsigned)(n >> G::LG), nvec), dim3(G::TPB), 0, st, v, work, tw, p);
+    hipLaunchKernelGGL((k_gfft_local<F, WB>), dim3((unsigned)(n >> G::LG), nvec), dim3(G::TPB), 0, st, v, work, tw, p, false);
     for (int s = G::LG; s < p; ++s)
-      hipLaunchKernelGGL((k_gfft_stage<F, WB>), dim3((unsigned)(n / 2 / G::TPB), nvec), dim3(G::TPB), 0, st, work, tw, p, s);
+      hipLaunchKernelGGL((k_gfft_stage<F, WB>), dim3((unsigned)(n / 2 / G::TPB), nvec), dim3(G::TPB), 0, st, work, tw, p, s, false);
     sp.end(st, fft_ms);
     sp.begin(st);
     hipLaunchKernelGGL(k_gfft_affine<F>, dim3((unsigned)(n / G::TPB), nvec), dim3(G::TPB), 0, st, work, v, tw, p);
@@ -134,7 +135,7 @@ void run_levels(const Vecs& v, int nvec, int power, uint32_t* work, const uint32
   }
   const int top = std::min(power, G::LG);
   sp.begin(st);  // the small levels' affine conversion is inside their one launch
-  hipLaunchKernelGGL((k_gfft_local<F, WB>), dim3(top + 1, nvec), dim3(G::TPB), 0, st, v, work, tw, -1);
+  hipLaunchKernelGGL((k_gfft_local<F, WB>), dim3(top + 1, nvec), dim3(G::TPB), 0, st, v, work, tw, -1, false);
   sp.end(st, fft_ms);
   HIPX(hipGetLastError());
   t.launches += 1;
@@ -166,7 +167,7 @@ void require_free(size_t bytes) {
   size_t free_b = 0, total_b = 0;
   HIPX(hipMemGetInfo(&free_b, &total_b));
   if (bytes > free_b)
-    throw ZkpError(ZKP_ERR_OUT_OF_MEMORY, "group iFFT: the working set of " + std::to_string(bytes >> 20) +
+    throw ZkpError(ZKP_ERR_OUT_OF_MEMORY, "group FFT: the working set of " + std::to_string(bytes >> 20) +
                                               " MiB does not fit in " + std::to_string(free_b >> 20) + " MiB of free HBM");
 }
 
@@ -174,8 +175,12 @@ void require_free(size_t bytes) {
 
 PrepareTimings ptau_prepare_timings() { return g_timings; }
 
-void group_ifft(int device, bool g2, const uint8_t* points, int log_n, uint8_t* out) {
-  if (log_n < 0 || log_n > gfft::MAX_LOG_N) throw ZkpError(ZKP_ERR_INVALID_ARG, "group iFFT: log_n must be within 0..28");
+namespace {
+
+// one transform of n = 2^log_n points, either direction; kernel_ms (if asked for): the launches' device time
+void group_transform(int device, bool g2, const uint8_t* points, int log_n, uint8_t* out, bool fwd, double* kernel_ms) {
+  if (log_n < 0 || log_n > gfft::MAX_LOG_N)
+    throw ZkpError(ZKP_ERR_INVALID_ARG, std::string(fwd ? "group FFT" : "group iFFT") + ": log_n must be within 0..28");
   HIPX(hipSetDevice(device));
   const size_t n = (size_t)1 << log_n, pb = g2 ? 128 : 64;
   const size_t ww = g2 ? work_words<Fq2>(log_n, 1) : work_words<Fq>(log_n, 1);
@@ -194,24 +199,42 @@ void group_ifft(int device, bool g2, const uint8_t* points, int log_n, uint8_t* 
     using G = Geom<F>;
     constexpr int WB = decltype(wb)::value;
     if (log_n > G::LG) {
-      hipLaunchKernelGGL((k_gfft_local<F, WB>), dim3((unsigned)(n >> G::LG), 1), dim3(G::TPB), 0, st, v, work.get(), tw.get(), log_n);
+      hipLaunchKernelGGL((k_gfft_local<F, WB>), dim3((unsigned)(n >> G::LG), 1), dim3(G::TPB), 0, st, v, work.get(), tw.get(), log_n, fwd);
       for (int s = G::LG; s < log_n; ++s)
-        hipLaunchKernelGGL((k_gfft_stage<F, WB>), dim3((unsigned)(n / 2 / G::TPB), 1), dim3(G::TPB), 0, st, work.get(), tw.get(), log_n, s);
+        hipLaunchKernelGGL((k_gfft_stage<F, WB>), dim3((unsigned)(n / 2 / G::TPB), 1), dim3(G::TPB), 0, st, work.get(), tw.get(), log_n, s, fwd);
       hipLaunchKernelGGL(k_gfft_affine<F>, dim3((unsigned)(n / G::TPB), 1), dim3(G::TPB), 0, st, work.get(), v, tw.get(), log_n);
     } else {
       // the small launch computes levels 0..log_n of the vector's prefixes; level log_n is the answer
-      hipLaunchKernelGGL((k_gfft_local<F, WB>), dim3(log_n + 1, 1), dim3(G::TPB), 0, st, v, work.get(), tw.get(), -1);
+      hipLaunchKernelGGL((k_gfft_local<F, WB>), dim3(log_n + 1, 1), dim3(G::TPB), 0, st, v, work.get(), tw.get(), -1, fwd);
     }
     HIPX(hipGetLastError());
   };
   using W1 = std::integral_constant<int, 1>;
   using W2 = std::integral_constant<int, 2>;
+  Event e0(true), e1(true);
+  HIPX(hipEventRecord(e0, st));
   if (g2)
     window_bits(true) == 2 ? one(Fq2{}, W2{}) : one(Fq2{}, W1{});
   else
     window_bits(false) == 2 ? one(Fq{}, W2{}) : one(Fq{}, W1{});
+  HIPX(hipEventRecord(e1, st));
   HIPX(hipMemcpyAsync(out, dout.get() + (n - 1) * pb / 4, n * pb, hipMemcpyDeviceToHost, st));
   HIPX(hipStreamSynchronize(st));
+  if (kernel_ms) {
+    float ms = 0;
+    HIPX(hipEventElapsedTime(&ms, e0, e1));
+    *kernel_ms = ms;
+  }
+}
+
+}  // namespace
+
+void group_ifft(int device, bool g2, const uint8_t* points, int log_n, uint8_t* out, double* kernel_ms) {
+  group_transform(device, g2, points, log_n, out, false, kernel_ms);
+}
+
+void group_fft(int device, bool g2, const uint8_t* points, int log_n, uint8_t* out, double* kernel_ms) {
+  group_transform(device, g2, points, log_n, out, true, kernel_ms);
 }
 
 std::vector<uint8_t> ptau_prepare_phase2(int device, const uint8_t* ptau, size_t len) {

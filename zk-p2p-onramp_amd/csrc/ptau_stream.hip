@@ -111,6 +111,7 @@ void launch_decompress(bool g2, const uint32_t* in, size_t n, uint64_t base, con
 }
 
 // what a pass that counts bad points throws for the first of them: "<prefix>[section <id> ]point <i><cause>"
+// (a job with a name: "<prefix><name> point <i><cause>")
 struct Refusal {
   zkp_status status;
   const char* prefix;
@@ -132,7 +133,8 @@ void run_chunks(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector
     const Job& j = jobs[c.job];
     HIPX(hipEventSynchronize(s.done));
     if (refusal && s.hbad[0])
-      throw ZkpError(refusal->status, std::string(refusal->prefix) + (j.id ? "section " + std::to_string(j.id) + " " : "") +
+      throw ZkpError(refusal->status, std::string(refusal->prefix) +
+                                          (j.name ? std::string(j.name) + " " : j.id ? "section " + std::to_string(j.id) + " " : "") +
                                           "point " + std::to_string(s.hbad[1]) + refusal->cause);
     deliver(s, j, c);
     t.download_ms += wall_ms(t0);
@@ -277,6 +279,53 @@ void pstream::decode_scale_pass(Slot (&slot)[2], const std::vector<Job>& jobs, c
                  launch_decode(j.g2, s.b, c.m, c.start, s.a, s.dbad, s.st);
                  sp.end(s.st, &t.decode_ms);
                });
+}
+
+void pstream::convert_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, int wb,
+                           const Convert& cv, Spans& sp, PtauChallengeTimings& t) {
+  ToZkey tz;
+  pscale::fill_to_zkey(tz.w);
+  const Refusal refusal{ZKP_ERR_FORMAT, cv.prefix, " is not on the curve"};
+  auto dest = [&](const Job& j) { return cv.out_u ? j.out_enc : j.out; };
+  run_chunks(
+      slot, jobs, chunks, nullptr, &refusal, t, true,
+      [&](Slot& s, const Job& j, const Chunk& c) {
+        const size_t bytes = c.m * j.pb();
+        if (cv.in_u) {
+          // b is free until the result is written to it: the staging buffer of the uncompressed bytes
+          upload(s, s.b, j.in + c.start * j.pb(), bytes, t);
+          points_bad_reset(s.dbad, s.st);
+          sp.begin(s.st);
+          launch_decode(j.g2, s.b, c.m, c.start, s.a, s.dbad, s.st);
+          sp.end(s.st, &t.decode_ms);
+        } else {
+          upload(s, s.a, j.in + c.start * j.pb(), bytes, t);
+          points_bad_reset(s.dbad, s.st);
+        }
+        sp.begin(s.st);
+        points_check_resident(j.g2, s.a, c.m, c.start, s.dbad, s.st);
+        sp.end(s.st, &t.parse_check_ms);
+        HIPX(hipMemcpyAsync(s.hbad.get(), s.dbad.get(), 16, hipMemcpyDeviceToHost, s.st));
+        if (!dest(j)) return;
+        const uint32_t* src = s.b;
+        if (j.scale) {
+          Powers pw;
+          pscale::fill_powers(pw, j.first, j.ratio, c.start);
+          sp.begin(s.st);
+          launch_scale(j.g2, wb, s.a, c.m, pw, cv.out_u ? nullptr : s.b.get(), cv.out_u ? s.b.get() : nullptr, nullptr, s.st);
+          sp.end(s.st, j.g2 ? &t.g2_ms : &t.g1_ms);
+        } else if (cv.out_u) {
+          sp.begin(s.st);
+          launch_encode(j.g2, s.a, c.m, tz, nullptr, s.b, nullptr, s.st);
+          sp.end(s.st, &t.encode_ms);
+        } else {
+          src = s.a;
+        }
+        HIPX(hipMemcpyAsync(s.hlem.get(), src, bytes, hipMemcpyDeviceToHost, s.st));
+      },
+      [&](Slot& s, const Job& j, const Chunk& c) {
+        if (dest(j)) std::memcpy(dest(j) + c.start * j.pb(), s.hlem.get(), c.m * j.pb());
+      });
 }
 
 void pstream::encode_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, HashFeed& feed,

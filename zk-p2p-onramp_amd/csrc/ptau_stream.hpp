@@ -65,6 +65,8 @@ struct Job {  // one section
   uint8_t* out;       // zkey layout (null: not wanted)
   uint32_t first[8], ratio[8];
   uint8_t* out_enc = nullptr;  // the pass's encoded stream, if it is kept and not only hashed
+  const char* name = nullptr;  // convert_pass: what a refusal calls the section ("<name> point <i>")
+  bool scale = false;          // convert_pass: whether the points are multiplied by first * ratio^i
   size_t pb() const { return g2 ? 128 : 64; }  // bytes of a point in the zkey layout
 };
 struct Chunk {
@@ -111,6 +113,17 @@ void encode_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vecto
 // bytes to the hashing thread.  A refused point is ZKP_ERR_FORMAT "response: ...".
 void decompress_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, HashFeed& feed,
                      Spans& sp, PtauChallengeTimings& t);
+
+// The MPCParams passes of zkey_bellman.hip.  Each job's `in` is uncompressed (in_u) or in the zkey layout; every
+// point is decoded (in_u) and checked, a job with `scale` multiplied by first * ratio^i, and the result leaves
+// uncompressed into out_enc (out_u) or in the zkey layout into out.  A job without that output is only checked.
+// A refused point is ZKP_ERR_FORMAT "<prefix><name> point <i> is not on the curve".
+struct Convert {
+  bool in_u, out_u;
+  const char* prefix;
+};
+void convert_pass(Slot (&slot)[2], const std::vector<Job>& jobs, const std::vector<Chunk>& chunks, int wb, const Convert& cv,
+                  Spans& sp, PtauChallengeTimings& t);
 
 // ptau_challenge.hpp's points_decompress (compressed: k_decompress_points) and points_from_uncompressed
 // (k_decode_points): chunks of ZKP_PTAU_CHUNK points on one stream (points_through.hpp)

@@ -17,6 +17,7 @@
 #include "device_pipeline.hpp"
 #include "mpc.hpp"
 #include "points_through.hpp"
+#include "ptau_scale_kernels.hpp"
 #include "qap.hpp"
 #include "spans.hpp"
 #include "zkey_verify.hpp"
@@ -66,6 +67,37 @@ __global__ __launch_bounds__(TPB) void k_rlc_coeffs(Seed8 seed, uint64_t first_i
     uint4* o = reinterpret_cast<uint4*>(out + (idx - first_index) * 8);
     o[0] = make_uint4(x[4 * j], x[4 * j + 1], x[4 * j + 2], x[4 * j + 3]);
     o[1] = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
+// sum_(i < n) r_i * base * ratio^i over the chunk's coefficients (8-word standard form, as k_rlc_coeffs writes
+// them): every thread one term, the block's sum by a tree in LDS into part[blockIdx.x] (8 words, standard
+// form); the host adds the blocks.  pw: pscale::fill_powers(1, w, chunk start), so base = w^start.
+__global__ __launch_bounds__(TPB) void k_rlc_power_sum(const uint32_t* __restrict__ coeffs, size_t n, pscale::Powers pw,
+                                                       uint32_t* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) uint32_t sh[TPB * 8];
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  Fr term = fe_zero<FrCfg>();
+  if (i < n) {
+    Fr t = load_fe<FrCfg>(pw.base);
+#pragma unroll
+    for (int b = 0; b < pscale::POW_BITS; ++b)
+      if ((i >> b) & 1) t = mul(t, load_fe<FrCfg>(pw.pw[b]));
+    term = mul(t, to_mont(load_fe<FrCfg>(coeffs + i * 8)));
+  }
+  store_fe(sh + threadIdx.x * 8, canon(term));
+  __syncthreads();
+  for (int half = TPB / 2; half > 0; half >>= 1) {
+    if ((int)threadIdx.x < half) {
+      const Fr a = load_fe<FrCfg>(sh + threadIdx.x * 8), b = load_fe<FrCfg>(sh + (threadIdx.x + half) * 8);
+      store_fe(sh + threadIdx.x * 8, canon(add(a, b)));
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    uint32_t w[8];
+    gfft::fr_words(load_fe<FrCfg>(sh), w);
+    pscale::store8(part + (size_t)blockIdx.x * 8, w);
   }
 }
 
@@ -232,11 +264,20 @@ void points_check_resident(bool g2, const uint32_t* d_points, size_t n, uint64_t
 }
 
 RlcResult rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* a, const uint8_t* b,
-                 size_t n) {
+                 size_t n, bool on_hyperplane) {
   const auto t_begin = std::chrono::steady_clock::now();
   check_index_range(first_index, n);
   RlcResult res;
   if (!n) return res;
+  int log_n = 0;
+  while ((size_t(1) << log_n) < n) ++log_n;
+  if (on_hyperplane && ((size_t(1) << log_n) != n || log_n > 28))
+    throw ZkpError(ZKP_ERR_INVALID_ARG, "rlc: the hyperplane rule wants 2^p points, p <= 28");
+  // w = Fr.w[log_n] and the running sum_(j < n - 1) r_j w^j (on_hyperplane)
+  uint32_t w_words[8];
+  for (int i = 0; i < 8; ++i) w_words[i] = FR_ROOTS_W[log_n][i];
+  const uint32_t one_words[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+  host::Fr power_sum = host::Fr::zero();
   const size_t CH = std::min(n, verify_chunk_points()), nchunks = (n + CH - 1) / CH, tail = n % CH;
   HIPX(hipSetDevice(device));
   Stream st(hipStreamNonBlocking), sup(hipStreamNonBlocking);  // first: destroyed after what runs on them
@@ -255,6 +296,9 @@ RlcResult rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const 
   MsmEngine eng(Curve::G1, prm, CH, st);
   const size_t ww = eng.window_words();
   DevBuf<> ds(CH * 8), dwin(2 * ww);
+  const size_t max_blocks = grid(CH);
+  DevBuf<> dpart(on_hyperplane ? max_blocks * 8 : 1);
+  PinnedBuf<uint32_t> hpart(on_hyperplane ? max_blocks * 8 : 1);
   DevBuf<unsigned long long> dbad(4);
   PinnedBuf<uint32_t> hwin(2 * ww);
   PinnedBuf<unsigned long long> hbad(4);
@@ -289,6 +333,18 @@ RlcResult rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const 
     const uint64_t first = first_index + at, blocks = ((first + m - 1) >> 2) - (first >> 2) + 1;
     hipLaunchKernelGGL(k_rlc_coeffs, dim3(grid(blocks)), dim3(TPB), 0, st, seed, first, (uint64_t)m, ds.get());
     HIPX(hipGetLastError());
+    // the last point's coefficient is not the stream's: it is left out of the sum and of the plan, and taken
+    // by the host after the loop
+    const bool has_last = on_hyperplane && k + 1 == nchunks;
+    const size_t m_sum = has_last ? m - 1 : m;
+    if (on_hyperplane && m_sum) {
+      pscale::Powers pw;
+      pscale::fill_powers(pw, one_words, w_words, at);
+      hipLaunchKernelGGL(k_rlc_power_sum, dim3(grid(m_sum)), dim3(TPB), 0, st, ds.get(), m_sum, pw, dpart.get());
+      HIPX(hipGetLastError());
+      HIPX(hipMemcpyAsync(hpart, dpart, (size_t)grid(m_sum) * 32, hipMemcpyDeviceToHost, st));
+    }
+    if (has_last) HIPX(hipMemsetAsync(ds.get() + (m - 1) * 8, 0, 32, st));
     HIPX(hipEventRecord(ev[2], st));
     launch_convert_fq_zkey(ba.row0(), m * 2, st);
     launch_convert_fq_zkey(bb.row0(), m * 2, st);
@@ -319,6 +375,29 @@ RlcResult rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const 
     const auto t0 = std::chrono::steady_clock::now();
     res.sum_a = host::jac_add(res.sum_a, msm_fold<HFq>(hwin, prm));
     res.sum_b = host::jac_add(res.sum_b, msm_fold<HFq>(hwin + ww, prm));
+    if (on_hyperplane)
+      for (size_t blk = 0; blk < (m_sum ? grid(m_sum) : 0); ++blk) {
+        host::U256 v;
+        for (int i = 0; i < 4; ++i) v.w[i] = (uint64_t)hpart[blk * 8 + 2 * i] | (uint64_t)hpart[blk * 8 + 2 * i + 1] << 32;
+        power_sum = power_sum + host::Fr::from_std(v);
+      }
+    res.t.fold_ms += wall_ms(t0);
+  }
+  if (on_hyperplane && res.first_bad_a == RLC_NO_BAD && res.first_bad_b == RLC_NO_BAD) {
+    // r'_(n-1) = -w sum_(j < n-1) r_j w^j: a full-width coefficient, two host scalar multiplications (both
+    // points were checked with their chunk)
+    const auto t0 = std::chrono::steady_clock::now();
+    host::U256 wv;
+    for (int i = 0; i < 4; ++i) wv.w[i] = (uint64_t)w_words[2 * i] | (uint64_t)w_words[2 * i + 1] << 32;
+    const host::U256 r_last = (host::Fr::from_std(wv) * power_sum).neg().to_std();
+    auto point = [&](const uint8_t* p) {
+      bool inf = true;
+      for (int i = 0; i < 64; ++i) inf &= p[i] == 0;
+      if (inf) return host::Jac<HFq>::inf();
+      return host::Jac<HFq>{HFq::raw(host::u256_from_le(p)), HFq::raw(host::u256_from_le(p + 32)), HFq::one()};
+    };
+    res.sum_a = host::jac_add(res.sum_a, host::jac_mul(point(a + (n - 1) * 64), r_last));
+    res.sum_b = host::jac_add(res.sum_b, host::jac_mul(point(b + (n - 1) * 64), r_last));
     res.t.fold_ms += wall_ms(t0);
   }
   res.t.total_ms = wall_ms(t_begin);

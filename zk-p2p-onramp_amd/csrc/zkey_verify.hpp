@@ -9,6 +9,18 @@
 // satisfy e(S_old, delta2_key) = e(S_new, delta2_init).  The verifier draws the r_i, so they are
 // uniform 128-bit values: a section that is not the initial one times delta_init / delta passes with
 // probability <= 2^-128, and the MSM runs ceil(129 / c) windows instead of ceil(255 / c).
+//
+// The H check.  A key that `zkey import bellman` wrote (zkey_bellman.hpp) carries an H section that differs from
+// the one a direct contribution writes by a multiple of (w^j)_j, n = 2^p the domain and w = Fr.w[p]: the
+// direction of the point B_(n-1) that an MPCParams file does not hold, and one that no prover's sum
+// sum_j q(x_j) H_j (q = h Z, deg h <= n - 2) has a component in.  snarkjs accepts such a key.  So the H
+// combination keeps the stream's r_j for points 0..n-2 and gives point n - 1 the coefficient
+//   r'_(n-1) = -w sum_(j < n-1) r_j w^j  (mod r),
+// which puts the coefficient vector on the hyperplane sum_j r_j w^j = 0, where the combination does not see
+// that direction.  The sum is a device reduction over the coefficient chunks (k_rlc_power_sum, each chunk with
+// its offset w^start); the one full-width coefficient is kept out of the 128-bit plan and taken by two host
+// scalar multiplications.  A wrong H section still passes with probability <= 2^-128 unless it differs from
+// the right one by a multiple of (w^j)_j.  The L check is unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -68,7 +80,10 @@ void points_check(int device, bool g2, const uint8_t* points, size_t n, uint64_t
 void points_bad_reset(unsigned long long* bad, hipStream_t st);
 void points_check_resident(bool g2, const uint32_t* d_points, size_t n, uint64_t base, unsigned long long* bad,
                            hipStream_t st);
-RlcResult rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* a, const uint8_t* b, size_t n);
+// on_hyperplane (n = 2^p, w = Fr.w[p]): points 0..n-2 keep the stream's coefficients r_j and point n - 1 takes
+// r' = -w sum_(j < n-1) r_j w^j mod r, so that sum_j r_j w^j = 0 (the H check below)
+RlcResult rlc_g1(int device, const uint8_t* seed32, uint64_t first_index, const uint8_t* a, const uint8_t* b, size_t n,
+                 bool on_hyperplane = false);
 
 // timings of one zkey_verify_frominit (ms)
 struct VerifyTimings {

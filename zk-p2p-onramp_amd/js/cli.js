@@ -28,9 +28,13 @@
  *   node cli.js powersoftau export challenge <in.ptau> <challenge> [-v]
  *   node cli.js powersoftau challenge contribute bn128 <challenge> <response> [-e=entropy] [-v]
  *   node cli.js powersoftau import response <old.ptau> <response> <new.ptau> [-n=|--name=name] [-v]
+ * and the same path in phase 2, over an MPCParams file that the Rust phase2 tools also read:
+ *   node cli.js zkey export bellman <circuit_xxxx.zkey> <circuit.mpcparams> [-v]
+ *   node cli.js zkey bellman contribute bn128 <circuit.mpcparams> <circuit_response.mpcparams> [-e=entropy] [-v]
+ *   node cli.js zkey import bellman <circuit_old.zkey> <circuit_response.mpcparams> <circuit_new.zkey> [-n=|--name=name] [-v]
  */
 const fs = require('fs');
-const { groth16, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, powersOfTau, wtns: wtnsApi, release } = require('./groth16');
+const { groth16, zKey, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, powersOfTau, wtns: wtnsApi, release } = require('./groth16');
 
 const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n' +
               '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
@@ -46,7 +50,10 @@ const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.
               '       cli.js powersoftau beacon <in.ptau> <out.ptau> <beaconHashHex> <numIterationsExp> [-n=name] [-v]\n' +
               '       cli.js powersoftau export challenge <in.ptau> <challenge> [-v]\n' +
               '       cli.js powersoftau challenge contribute bn128 <challenge> <response> [-e=entropy] [-v]\n' +
-              '       cli.js powersoftau import response <old.ptau> <response> <new.ptau> [-n=|--name=name] [-v]\n';
+              '       cli.js powersoftau import response <old.ptau> <response> <new.ptau> [-n=|--name=name] [-v]\n' +
+              '       cli.js zkey export bellman <circuit_xxxx.zkey> <circuit.mpcparams> [-v]\n' +
+              '       cli.js zkey bellman contribute bn128 <circuit.mpcparams> <circuit_response.mpcparams> [-e=entropy] [-v]\n' +
+              '       cli.js zkey import bellman <circuit_old.zkey> <circuit_response.mpcparams> <circuit_new.zkey> [-n=|--name=name] [-v]\n';
 
 async function main(argv) {
   if (argv.length === 5 && argv[0] === 'zkey' && argv[1] === 'export' && argv[2] === 'soliditycalldata') {
@@ -98,6 +105,35 @@ async function main(argv) {
     }
     if (argv[1] === 'import' && pos[2] === 'response' && pos.length === 6) {
       await powersOfTau.importResponse(pos[3], pos[4], pos[5], opt(/^(-n|--name)=/), true, logger);
+      return 0;
+    }
+    process.stderr.write(USAGE);
+    return 1;
+  }
+  if (argv[0] === 'zkey' && (argv[1] === 'bellman' || (['export', 'import'].includes(argv[1]) && argv[2] === 'bellman'))) {
+    const verbose = argv.includes('-v') || argv.includes('--verbose');
+    const logger = verbose ? { info: (m) => process.stdout.write(`[INFO]  snarkJS: ${m}\n`) } : undefined;
+    const pos = argv.filter((a) => !/^(-n|--name|-e|--entropy)=/.test(a) && a !== '-v' && a !== '--verbose');
+    const opt = (re) => {
+      const a = argv.find((x) => re.test(x));
+      return a === undefined ? undefined : a.replace(/^[^=]*=/, '');
+    };
+    if (argv[1] === 'export' && pos.length === 5) {
+      await zKey.exportBellman(pos[3], pos[4], logger);
+      return 0;
+    }
+    if (argv[1] === 'bellman' && pos[2] === 'contribute' && pos.length === 6) {
+      try {
+        await zKey.bellmanContribute(pos[3], pos[4], pos[5], opt(/^(-e|--entropy)=/), logger);
+      } catch (e) {  // an unknown curve: snarkjs' error line, exit 1
+        if (!/^Curve not supported/.test(e.message)) throw e;
+        process.stdout.write(`[ERROR] snarkJS: Error: ${e.message}\n`);
+        return 1;
+      }
+      return 0;
+    }
+    if (argv[1] === 'import' && pos.length === 6) {
+      await zKey.importBellman(pos[3], pos[4], pos[5], opt(/^(-n|--name)=/), logger);
       return 0;
     }
     process.stderr.write(USAGE);

@@ -409,6 +409,49 @@ async function importResponse(oldPtauName, responseName, newPtauName, name, impo
   return out;
 }
 
+/*
+ * snarkjs' `zKey.exportBellman(zkeyName, mpcparamsName, logger)` (the `zkey export bellman` step): the key as an
+ * MPCParams file, which an outside contributor (snarkjs' `zkey bellman contribute` or the Rust phase2 tools)
+ * works on without holding the key.  Section 9 goes through a forward group FFT on the GPU.
+ */
+async function exportBellman(zkeyName, mpcparamsName, logger, device) {
+  const out = addon.zkeyExportBellman(readInput(zkeyName), device || 0);
+  writeOutput(mpcparamsName, out);
+  if (logger && logger.info) logger.info(`zkey export bellman: ${out.length} bytes`);
+  return out;
+}
+
+/*
+ * snarkjs' `zKey.bellmanContribute(curve, challengeName, responseName, entropy, logger)` (the `zkey bellman
+ * contribute bn128` step): one contribution to an MPCParams file on the GPU.  Only bn128 exists here.  The
+ * contribution hash goes to logger.info in snarkjs' four-word rows; resolves to it, as snarkjs does.
+ */
+async function bellmanContribute(curve, challengeName, responseName, entropy, logger, device) {
+  requireBn128(curve);
+  const res = addon.zkeyBellmanContribute(readInput(challengeName), entropy == null ? '' : String(entropy), device || 0);
+  writeOutput(responseName, res.response);
+  if (logger && logger.info) {
+    const hex = res.hash.toString('hex');
+    const rows = [0, 1, 2, 3].map((r) => '\t\t' + [0, 1, 2, 3].map((c) => hex.substr(32 * r + 8 * c, 8)).join(' '));
+    logger.info('Contribution Hash: \n' + rows.join('\n'));
+  }
+  return res.hash;
+}
+
+/*
+ * snarkjs' `zKey.importBellman(zkeyNameOld, mpcparamsName, zkeyNameNew, name, logger)` (the `zkey import bellman`
+ * step): the key that follows the old one by the response's contribution.  Its section 9 differs from a direct
+ * contribution's by a multiple that no prover sees and `zkey verify` accepts; the contribution itself is checked
+ * by zKey.verifyFromR1cs on the result, not here.
+ */
+async function importBellman(zkeyNameOld, mpcparamsName, zkeyNameNew, name, logger, device) {
+  const out = addon.zkeyImportBellman(readInput(zkeyNameOld), readInput(mpcparamsName), name ? String(name) : undefined,
+                                      device || 0);
+  writeOutput(zkeyNameNew, out);
+  if (logger && logger.info) logger.info(`zkey import bellman ${name || ''}: ${out.length} bytes`);
+  return out;
+}
+
 function release() {
   for (const h of provers.values()) addon.freeProver(h);
   for (const h of memProvers.values()) addon.freeProver(h);
@@ -419,7 +462,8 @@ function release() {
 module.exports = {
   groth16: { prove, proveBatch },
   proveBatch,
-  zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit },
+  zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit, exportBellman,
+          bellmanContribute, importBellman },
   powersOfTau: { newAccumulator, contribute: contributePtau, beacon: beaconPtau, preparePhase2, verify: verifyPtau,
                  exportChallenge, challengeContribute, importResponse },
   wtns: { check: wtnsCheck, checkDetails: wtnsCheckDetails },

@@ -36,6 +36,19 @@ export declare const zKey: {
     Promise<boolean>;
   /** the same against the initial key `zkey new` wrote */
   verifyFromInit(initName: Input, zkeyName: Input, logger?: VerifyLogger, device?: number): Promise<boolean>;
+  /** `snarkjs zkey export bellman` on the GPU (zkp_zkey_export_bellman): the key as the MPCParams file an outside
+   *  contributor works on */
+  exportBellman(zkeyName: Input, mpcparamsName?: string | { type: "mem"; data?: Uint8Array }, logger?: Logger,
+    device?: number): Promise<Uint8Array>;
+  /** `snarkjs zkey bellman contribute bn128` on the GPU (zkp_zkey_bellman_contribute): the response file is written
+   *  to responseName; resolves to the 64-byte contribution hash; any curve but bn128 throws */
+  bellmanContribute(curve: string | { name: string }, challengeName: Input,
+    responseName?: string | { type: "mem"; data?: Uint8Array }, entropy?: string, logger?: Logger, device?: number):
+    Promise<Uint8Array>;
+  /** `snarkjs zkey import bellman` on the GPU (zkp_zkey_import_bellman): the key that follows zkeyNameOld by the
+   *  response's contribution.  The contribution is checked by verifyFromR1cs on the result, not here */
+  importBellman(zkeyNameOld: Input, mpcparamsName: Input, zkeyNameNew?: string | { type: "mem"; data?: Uint8Array },
+    name?: string, logger?: Logger, device?: number): Promise<Uint8Array>;
 };
 export declare const powersOfTau: {
   /** `snarkjs powersoftau new bn128 <power>`: a ceremony file of generators, no contribution; any curve but

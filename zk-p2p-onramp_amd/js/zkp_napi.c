@@ -22,6 +22,9 @@
  *   ptauChallengeContribute(challengeBuffer, entropy, device?, rand64?) -> Buffer (`powersoftau challenge contribute`)
  *   ptauImportResponse(ptauBuffer, responseBuffer, name?, device?) -> Buffer (`snarkjs powersoftau import response`)
  *   zkeyVerifyFromR1cs(r1csBuffer, ptauBuffer, zkeyBuffer, device?) -> {valid, message} (`zkey verify`)
+ *   zkeyExportBellman(zkeyBuffer, device?)     -> Buffer (`snarkjs zkey export bellman`)
+ *   zkeyBellmanContribute(mpcparamsBuffer, entropy, device?, rand64?) -> {response, hash} (`zkey bellman contribute`)
+ *   zkeyImportBellman(zkeyBuffer, responseBuffer, name?, device?) -> Buffer (`snarkjs zkey import bellman`)
  *   wtnsCheck(r1csBuffer, wtnsBuffer, device?) -> {valid, message, nBad, firstBad, bad, nConstraints} (`wtns check`)
  *   version()
  * prove()/proveBatch() run on the libuv threadpool (napi_async_work), so the JS main
@@ -514,6 +517,107 @@ static napi_value js_ptau_import_response(napi_env env, napi_callback_info info)
   return buffer_out(env, out, out_len);
 }
 
+/* zkeyExportBellman(zkeyBuffer, device?) -> Buffer: `snarkjs zkey export bellman` (zkp_zkey_export_bellman),
+ * synchronous -- a setup step */
+static napi_value js_zkey_export_bellman(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &b0);
+  if (!b0) {
+    napi_throw_type_error(env, NULL, "zkeyExportBellman(zkeyBuffer, device?)");
+    return NULL;
+  }
+  int device = 0;
+  if (argc > 1) napi_get_value_int32(env, argv[1], &device);
+  void* zkey;
+  size_t zkey_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &zkey, &zkey_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  zkp_status st = zkp_zkey_export_bellman(device, (const uint8_t*)zkey, zkey_len, &out, &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return buffer_out(env, out, out_len);
+}
+
+/* zkeyBellmanContribute(mpcparamsBuffer, entropyString, device?, rand64Buffer?) -> {response: Buffer, hash: Buffer}:
+ * `snarkjs zkey bellman contribute bn128` (zkp_zkey_bellman_contribute; rand64: the 64 random bytes mixed with
+ * the entropy, default the OS CSPRNG; hash: the 64-byte contribution hash), synchronous */
+static napi_value js_zkey_bellman_contribute(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false, b3 = false;
+  char ent[4096];
+  const char* e = NULL;
+  if (argc >= 2) {
+    napi_is_buffer(env, argv[0], &b0);
+    e = opt_string(env, argv[1], ent, sizeof ent);
+  }
+  void* rand64 = NULL;
+  size_t rand_len = 0;
+  if (argc > 3) {
+    napi_is_buffer(env, argv[3], &b3);
+    if (b3) NAPI_CALL(env, napi_get_buffer_info(env, argv[3], &rand64, &rand_len));
+  }
+  if (!b0 || !e || (b3 && rand_len != 64)) {
+    napi_throw_type_error(env, NULL, "zkeyBellmanContribute(mpcparamsBuffer, entropyString, device?, rand64Buffer?)");
+    return NULL;
+  }
+  int device = 0;
+  if (argc > 2) napi_get_value_int32(env, argv[2], &device);
+  void* ch;
+  size_t ch_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &ch, &ch_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  uint8_t hash[64];
+  zkp_status st = zkp_zkey_bellman_contribute(device, (const uint8_t*)ch, ch_len, (const uint8_t*)rand64, e, &out, &out_len, hash);
+  if (st != ZKP_OK) return throw_status(env, st);
+  napi_value response = buffer_out(env, out, out_len);
+  if (!response) return NULL;
+  napi_value res, hbuf;
+  void* hdst = NULL;
+  NAPI_CALL(env, napi_create_buffer(env, sizeof hash, &hdst, &hbuf));
+  memcpy(hdst, hash, sizeof hash);
+  NAPI_CALL(env, napi_create_object(env, &res));
+  NAPI_CALL(env, napi_set_named_property(env, res, "response", response));
+  NAPI_CALL(env, napi_set_named_property(env, res, "hash", hbuf));
+  return res;
+}
+
+/* zkeyImportBellman(zkeyBuffer, responseBuffer, nameString?, device?) -> Buffer: `snarkjs zkey import bellman`
+ * (zkp_zkey_import_bellman), synchronous */
+static napi_value js_zkey_import_bellman(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false, b1 = false;
+  if (argc >= 2) {
+    napi_is_buffer(env, argv[0], &b0);
+    napi_is_buffer(env, argv[1], &b1);
+  }
+  if (!b0 || !b1) {
+    napi_throw_type_error(env, NULL, "zkeyImportBellman(zkeyBuffer, responseBuffer, nameString?, device?)");
+    return NULL;
+  }
+  char name[256];
+  const char* nm = argc > 2 ? opt_string(env, argv[2], name, sizeof name) : NULL;
+  int device = 0;
+  if (argc > 3) napi_get_value_int32(env, argv[3], &device);
+  void *zkey, *resp;
+  size_t zkey_len, resp_len;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &zkey, &zkey_len));
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &resp, &resp_len));
+  uint8_t* out = NULL;
+  size_t out_len = 0;
+  zkp_status st = zkp_zkey_import_bellman(device, (const uint8_t*)zkey, zkey_len, (const uint8_t*)resp, resp_len, nm, &out,
+                                          &out_len);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return buffer_out(env, out, out_len);
+}
+
 static napi_value js_load(napi_env env, napi_callback_info info) {
   size_t argc = 2;
   napi_value argv[2];
@@ -917,6 +1021,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"ptauImportResponse", NULL, js_ptau_import_response, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyVerifyFromR1cs", NULL, js_zkey_verify_r1cs, NULL, NULL, NULL, napi_default, NULL},
       {"wtnsCheck", NULL, js_wtns_check, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyExportBellman", NULL, js_zkey_export_bellman, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyBellmanContribute", NULL, js_zkey_bellman_contribute, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyImportBellman", NULL, js_zkey_import_bellman, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

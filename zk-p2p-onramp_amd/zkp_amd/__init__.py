@@ -206,6 +206,19 @@ def load_library(path: str = LIB_PATH):
                          "zkp_ptau_challenge_timings", "zkp_points_decompress", "zkp_points_from_uncompressed",
                          "zkp_field_sqrt"):
                 getattr(lib, name).restype = ctypes.c_int
+        if hasattr(lib, "zkp_zkey_import_bellman"):  # zkey export bellman / bellman contribute / import bellman
+            u32p = ctypes.POINTER(ctypes.c_uint32)
+            lib.zkp_group_fft.argtypes = [ctypes.c_int, ctypes.c_int, u8p, ctypes.c_int, u8p]
+            lib.zkp_mpcparams_info.argtypes = [u8p, sz, u32p, u32p, u32p, u32p]
+            lib.zkp_zkey_export_bellman.argtypes = [ctypes.c_int, u8p, sz, ctypes.POINTER(u8p), ctypes.POINTER(sz)]
+            lib.zkp_zkey_bellman_contribute.argtypes = [ctypes.c_int, u8p, sz, u8p, ctypes.c_char_p, ctypes.POINTER(u8p),
+                                                        ctypes.POINTER(sz), u8p]
+            lib.zkp_zkey_import_bellman.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, ctypes.c_char_p, ctypes.POINTER(u8p),
+                                                    ctypes.POINTER(sz)]
+            lib.zkp_zkey_bellman_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+            for name in ("zkp_group_fft", "zkp_mpcparams_info", "zkp_zkey_export_bellman", "zkp_zkey_bellman_contribute",
+                         "zkp_zkey_import_bellman", "zkp_zkey_bellman_timings"):
+                getattr(lib, name).restype = ctypes.c_int
         if hasattr(lib, "zkp_wtns_check"):  # wtns check
             rp = ctypes.POINTER(_CheckResult)
             u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -743,6 +756,19 @@ def group_ifft(points: bytes, log_n: int, g2: bool = False, device: int = 0) -> 
     return bytes(out)
 
 
+def group_fft(points: bytes, log_n: int, g2: bool = False, device: int = 0) -> bytes:
+    """Kernel-level (zkp_group_fft): out_c = sum_j w^(c j) P_j over the n = 2^log_n zkey-layout points
+    (w = Fr.w[log_n]), natural order in and out, no n^-1: group_ifft(group_fft(x)) == x."""
+    pb = 128 if g2 else 64
+    if log_n < 0 or len(points) != pb << log_n:
+        raise ValueError("group_fft: points must hold 2^log_n points of %d bytes" % pb)
+    pp, pk = _buf(points)
+    out = (ctypes.c_uint8 * len(points))()
+    _check(load_library().zkp_group_fft(device, 1 if g2 else 0, pp, log_n,
+                                        ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8))))
+    return bytes(out)
+
+
 def _seed(seed):
     if seed is None:
         return None, None
@@ -1079,6 +1105,71 @@ def ptau_challenge_timings() -> dict:
     _check(load_library().zkp_ptau_challenge_timings(out, 14))
     keys = ["total", "parse_point_check", "challenge_hash", "key", "upload", "decode", "g1_decompress", "g2_decompress",
             "g1_scale", "g2_scale", "encode", "download", "hash_threads", "chunks"]
+    return dict(zip(keys, list(out)))
+
+
+def mpcparams_info(data: bytes) -> dict:
+    """Host only (zkp_mpcparams_info): the counts of an MPCParams file, its layout validated (ZkpError
+    ZKP_ERR_FORMAT "mpcparams: ..." otherwise)."""
+    dp, dlen, dk = _in(data)
+    v = [ctypes.c_uint32() for _ in range(4)]
+    _check(load_library().zkp_mpcparams_info(dp, dlen, *[ctypes.byref(x) for x in v]))
+    return dict(zip(["n_public", "domain_size", "n_vars", "n_contributions"], [x.value for x in v]))
+
+
+def zkey_export_bellman(zkey: bytes, device: int = 0) -> bytes:
+    """`snarkjs zkey export bellman <circuit.zkey> <circuit.mpcparams>` (zkp_zkey_export_bellman): the key as an
+    MPCParams file; section 9 goes through the forward group FFT and a coset scaling into the n - 1 points
+    delta^-1 tau^i (tau^n - 1) G1."""
+    lib = load_library()
+    zp, zlen, zk = _in(zkey)
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_zkey_export_bellman(device, zp, zlen, ctypes.byref(out), ctypes.byref(n)))
+    return _take(lib, out, n)
+
+
+def zkey_bellman_contribute(challenge: bytes, entropy: str, rand64: bytes = None, device: int = 0, with_hash: bool = False):
+    """`snarkjs zkey bellman contribute bn128 <circuit.mpcparams> <response.mpcparams> -e=<entropy>`
+    (zkp_zkey_bellman_contribute): one contribution to an MPCParams file on the GPU, drawn as
+    zkey_contribute_entropy draws it -> the response file; with_hash: (response, the 64-byte contribution hash)."""
+    lib = load_library()
+    cp, clen, ck = _in(challenge)
+    rp = None
+    if rand64 is not None:
+        if len(rand64) != 64:
+            raise ValueError("rand64 must be 64 bytes")
+        rp, rk = _buf(bytes(rand64))
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    h = (ctypes.c_uint8 * 64)()
+    _check(lib.zkp_zkey_bellman_contribute(device, cp, clen, rp, entropy.encode(), ctypes.byref(out), ctypes.byref(n),
+                                           ctypes.cast(h, ctypes.POINTER(ctypes.c_uint8))))
+    res = _take(lib, out, n)
+    return (res, bytes(h)) if with_hash else res
+
+
+def zkey_import_bellman(old_zkey: bytes, response: bytes, name=None, device: int = 0) -> bytes:
+    """`snarkjs zkey import bellman <old.zkey> <response.mpcparams> <new.zkey> [-n=]` (zkp_zkey_import_bellman): the
+    key that follows old_zkey by the response's contribution.  Its section 9 differs from a direct contribution's
+    by a multiple of (w^j)_j, which zkey_verify accepts; the contribution itself is checked by zkey_verify on the
+    result, not here."""
+    lib = load_library()
+    zp, zlen, zk = _in(old_zkey)
+    rp, rlen, rk = _in(response)
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    n = ctypes.c_size_t()
+    _check(lib.zkp_zkey_import_bellman(device, zp, zlen, rp, rlen, None if name is None else name.encode(),
+                                       ctypes.byref(out), ctypes.byref(n)))
+    return _take(lib, out, n)
+
+
+def zkey_bellman_timings() -> dict:
+    """ms of the calling thread's last export / bellman contribute / import (zkp_zkey_bellman_timings)."""
+    out = (ctypes.c_double * 11)()
+    _check(load_library().zkp_zkey_bellman_timings(out, 11))
+    keys = ["total", "parse", "upload", "decode", "point_check", "scale", "transform", "coset_scale", "encode", "download",
+            "chunks"]
     return dict(zip(keys, list(out)))
 
 
