@@ -669,6 +669,63 @@ zkp_status zkp_wtns_check_timings(double* ms, int n);
  * it (ZKP_WTNS_CHECK_LONG at load overrides the default; 0: none does).  n = capacity. */
 zkp_status zkp_checker_paths(const zkp_checker* c, uint64_t* out, int n);
 
+/* ---- `zkey export verificationkey` and `groth16 verify` from a verification key ----
+ * zkp_zkey_export_vkey (host only): snarkjs' verification_key.json of a key's sections 2 and 3, as
+ * JSON.stringify(vKey, null, 1): keys protocol, curve, nPublic, vk_alpha_1, vk_beta_2, vk_gamma_2, vk_delta_2,
+ * vk_alphabeta_12, IC in this order, points as projective decimal strings with the "1" / ["1","0"] tails.  The
+ * layout is restated from memory (format-unpinned).  Buffer contract of zkp_proof_json: buf may be NULL to query
+ * *needed (terminator included); a buf that is too small is ZKP_ERR_INVALID_ARG with *needed set.
+ *
+ * A zkp_verifier holds a verification key and verifies batches of proofs with the per-proof Miller loops on the
+ * GPU.  zkp_verifier_load_vkey_json parses a verification_key.json with a strict parser of its own: malformed
+ * JSON, a missing or mistyped field, a coordinate >= p, a point off its curve or (G2) outside the subgroup of
+ * order r, an IC whose length is not nPublic + 1, a vk_alphabeta_12 (optional) that is not e(vk_alpha_1, vk_beta_2)
+ * are ZKP_ERR_FORMAT with a zkp_last_error naming the field; another protocol is ZKP_ERR_PROTOCOL, another curve
+ * ZKP_ERR_CURVE.  zkp_verifier_load_zkey takes the same key from sections 2 and 3 of a .zkey under the same
+ * point checks.  Verification uses alpha and beta, never vk_alphabeta_12.
+ *
+ * zkp_verifier_verify: valid[i] (n bytes) = 1 iff proof i verifies, the verdict zkp_proof_verify gives for that
+ * proof under the same key; *n_valid (nullable) = their count.  Public signals come from proofs[i].public_signals;
+ * a proofs[i].n_public other than the key's (or a capacity below it) is ZKP_ERR_INVALID_ARG for the whole call.  A
+ * proof that merely fails -- a coordinate >= p, a point off its curve, a B outside the subgroup, a public signal
+ * >= r, a false pairing equation -- is ZKP_OK with valid[i] = 0.  n = 0 is ZKP_OK with *n_valid = 0.  The batch is
+ * checked by one randomised equation with 128-bit coefficients drawn from seed32 (zkp_rlc_coeffs' stream): an
+ * invalid proof is accepted with probability about 2^-128 over the seed.  seed32 = NULL takes the seed from the OS
+ * CSPRNG and is what a production call MUST pass; a caller-chosen seed is for tests only (whoever knows the seed
+ * before choosing the proofs can forge a batch).  Batches are processed in device passes of ZKP_VERIFY_CHUNK
+ * proofs (default 16384, 64..1048576; a malformed value is ZKP_ERR_INVALID_ARG), so n is unbounded.  Concurrent
+ * calls on one handle are serialised.
+ *
+ * zkp_verifier_timings: ms of the calling thread's last zkp_verifier_verify: [0] upload, coefficients and the
+ * per-proof gates, [1] the scalar multiplications r_i A_i, r_i C_i, [2] the Miller kernel, [3] the product kernel
+ * and the copies back, [4] host: s-vector, point sums and the three fixed-Q Miller loops, [5] the final
+ * exponentiation, [6] the tree search of a failing batch, [7] host wall of the call, [8] equations evaluated
+ * (a count, not ms).  n = capacity. */
+zkp_status zkp_zkey_export_vkey(const uint8_t* zkey, size_t len, char* buf, size_t cap, size_t* needed);
+typedef struct zkp_verifier zkp_verifier;
+zkp_status zkp_verifier_load_vkey_json(int device, const char* json, size_t len, zkp_verifier** out);
+zkp_status zkp_verifier_load_zkey(int device, const uint8_t* zkey, size_t len, zkp_verifier** out);
+zkp_status zkp_verifier_info(const zkp_verifier* v, uint32_t* n_public);
+zkp_status zkp_verifier_verify(zkp_verifier* v, const zkp_proof* proofs, size_t n,
+                               const uint8_t* seed32 /* NULL: OS CSPRNG (production) */, uint8_t* valid /* n bytes */,
+                               size_t* n_valid);
+zkp_status zkp_verifier_timings(double* ms, int n);
+void zkp_verifier_free(zkp_verifier* v);
+
+/* ---- kernel-level pairing entry points (tests and benchmarks) ----
+ * zkp_miller_loop: n optimal-ate Miller loops on the device, one per lane.  g1: n x 64, g2: n x 128 bytes,
+ * standard-form LE, all-zero = infinity (such a pair gives 1); the points are the caller's to validate (on their
+ * curves, g2 of order r).  out: n x 384 bytes in zkp_pairing's coefficient order.  The device keeps T and P
+ * projective and never inverts, so each value is the host's Miller value times a factor of Fq2 that the final
+ * exponentiation removes: zkp_final_exponentiation(out_i) == zkp_pairing(g1_i, g2_i), and device Miller values
+ * may be compared with anything only after it.
+ * zkp_final_exponentiation (host): ffjavascript's final exponentiation of one Fq12 value.
+ * zkp_fq12_product: the product of n Fq12 values (n x 384 bytes, coordinates < p) by the reduction kernel, the
+ * last few factors multiplied on the host; n = 0 gives 1. */
+zkp_status zkp_miller_loop(int device, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out);
+zkp_status zkp_final_exponentiation(const uint8_t* in384, uint8_t* out384);
+zkp_status zkp_fq12_product(int device, const uint8_t* in, size_t n, uint8_t* out384);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 #include "../../include/zkp_amd.h"
 #include "beacon.hpp"
 #include "device_pipeline.hpp"
+#include "groth16_verify.hpp"
 #include "hip_check.hpp"
 #include "host_ec.hpp"
 #include "host_pairing.hpp"
@@ -39,6 +40,10 @@ static_assert(sizeof(zkp_partial) == 392, "zkp_partial is exchanged as 392 raw b
 
 struct zkp_prover {
   zkp::Prover* impl;
+};
+
+struct zkp_verifier {
+  std::unique_ptr<zkp::Verifier> impl;
 };
 
 namespace {
@@ -850,6 +855,88 @@ zkp_status zkp_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* out384) {
     }
   });
 }
+
+zkp_status zkp_final_exponentiation(const uint8_t* in384, uint8_t* out384) {
+  if (!in384 || !out384) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] {
+    HFq2 c[6];
+    for (int i = 0; i < 6; ++i) c[i] = HFq2{fq_std(in384 + 64 * i), fq_std(in384 + 64 * i + 32)};
+    const zkp::host::Fq12 f =
+        zkp::host::final_exponentiation(zkp::host::Fq12{{c[0], c[1], c[2]}, {c[3], c[4], c[5]}});
+    const HFq2* o[6] = {&f.c0.c0, &f.c0.c1, &f.c0.c2, &f.c1.c0, &f.c1.c1, &f.c1.c2};
+    for (int i = 0; i < 6; ++i) {
+      zkp::host::u256_to_le(o[i]->c0.to_std(), out384 + 64 * i);
+      zkp::host::u256_to_le(o[i]->c1.to_std(), out384 + 64 * i + 32);
+    }
+  });
+}
+
+zkp_status zkp_miller_loop(int device, const uint8_t* g1, const uint8_t* g2, size_t n, uint8_t* out) {
+  if (n && (!g1 || !g2 || !out)) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] { zkp::miller_loop_points(device, g1, g2, n, out); });
+}
+
+zkp_status zkp_fq12_product(int device, const uint8_t* in, size_t n, uint8_t* out384) {
+  if ((n && !in) || !out384) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  return guard([&] {
+    for (size_t i = 0; i < n * 12; ++i)
+      if (zkp::host::u256_geq(zkp::host::u256_from_le(in + 32 * i), zkp::host::FQ_DESC.mod))
+        throw zkp::ZkpError(ZKP_ERR_INVALID_ARG, "fq12_product: coordinate >= p");
+    zkp::fq12_product(device, in, n, out384);
+  });
+}
+
+zkp_status zkp_zkey_export_vkey(const uint8_t* zkey, size_t len, char* buf, size_t cap, size_t* needed) {
+  if (!zkey) return fail(ZKP_ERR_INVALID_ARG, "null zkey");
+  std::string s;
+  const zkp_status st = guard([&] { s = zkp::vkey_json(zkp::vkey_from_zkey(zkey, len)); });
+  if (st != ZKP_OK) return st;
+  return emit(s, buf, cap, needed);
+}
+
+zkp_status zkp_verifier_load_vkey_json(int device, const char* json, size_t len, zkp_verifier** out) {
+  if (!json || !out) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  return guard([&] {
+    auto v = std::make_unique<zkp_verifier>();
+    v->impl = std::make_unique<zkp::Verifier>(device, zkp::parse_vkey_json(json, len));
+    *out = v.release();
+  });
+}
+
+zkp_status zkp_verifier_load_zkey(int device, const uint8_t* zkey, size_t len, zkp_verifier** out) {
+  if (!zkey || !out) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  *out = nullptr;
+  return guard([&] {
+    auto v = std::make_unique<zkp_verifier>();
+    v->impl = std::make_unique<zkp::Verifier>(device, zkp::vkey_from_zkey(zkey, len));
+    *out = v.release();
+  });
+}
+
+zkp_status zkp_verifier_info(const zkp_verifier* v, uint32_t* n_public) {
+  if (!v || !v->impl) return fail(ZKP_ERR_INVALID_ARG, "null verifier");
+  if (n_public) *n_public = v->impl->n_public();
+  return ZKP_OK;
+}
+
+zkp_status zkp_verifier_verify(zkp_verifier* v, const zkp_proof* proofs, size_t n, const uint8_t* seed32, uint8_t* valid,
+                               size_t* n_valid) {
+  if (!v || !v->impl || (n && (!proofs || !valid))) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  if (n_valid) *n_valid = 0;
+  return guard([&] { v->impl->verify(proofs, n, seed32, valid, n_valid); });
+}
+
+zkp_status zkp_verifier_timings(double* ms, int n) {
+  if (!ms || n < 0) return fail(ZKP_ERR_INVALID_ARG, "null argument");
+  const zkp::Groth16VerifyTimings& t = zkp::verify_timings();
+  const double v[9] = {t.gates_ms,     t.scalar_ms, t.miller_ms, t.product_ms, t.host_miller_ms,
+                       t.final_exp_ms, t.search_ms, t.total_ms,  t.node_checks};
+  for (int i = 0; i < n && i < 9; ++i) ms[i] = v[i];
+  return ZKP_OK;
+}
+
+void zkp_verifier_free(zkp_verifier* v) { delete v; }
 
 const char* zkp_last_error(void) { return g_err.c_str(); }
 

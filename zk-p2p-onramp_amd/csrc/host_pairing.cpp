@@ -237,6 +237,11 @@ Fq12 final_exponentiation(const Fq12& f) {
 
 Fq12 pairing(const Affine<Fq>& p, const Affine<Fq2>& q) { return final_exponentiation(miller_loop_multi(&p, &q, 1)); }
 
+void g2_frobenius_consts(Fq2& gx, Fq2& gy) {
+  gx = fc().gx;
+  gy = fc().gy;
+}
+
 bool g1_on_curve(const Affine<Fq>& p) {
   if (p.inf) return true;
   return p.y.sqr() == p.x.sqr() * p.x + fq_small(3);

@@ -31,6 +31,8 @@ Fq12 miller_loop_multi(const Affine<Fq>* ps, const Affine<Fq2>* qs, int n);
 Fq12 final_exponentiation(const Fq12& f);
 // snarkjs-convention GT element e(P, Q)
 Fq12 pairing(const Affine<Fq>& p, const Affine<Fq2>& q);
+// the G2 Frobenius pi(x, y) = (conj(x) gx, conj(y) gy): gx = xi^((p-1)/3), gy = xi^((p-1)/2)
+void g2_frobenius_consts(Fq2& gx, Fq2& gy);
 
 bool g1_on_curve(const Affine<Fq>& p);  // y^2 = x^3 + 3 (infinity: true)
 bool g2_on_curve(const Affine<Fq2>& p);  // y^2 = x^3 + 3/(9+u)

@@ -32,11 +32,17 @@
  *   node cli.js zkey export bellman <circuit_xxxx.zkey> <circuit.mpcparams> [-v]
  *   node cli.js zkey bellman contribute bn128 <circuit.mpcparams> <circuit_response.mpcparams> [-e=entropy] [-v]
  *   node cli.js zkey import bellman <circuit_old.zkey> <circuit_response.mpcparams> <circuit_new.zkey> [-n=|--name=name] [-v]
+ * and the two ends of the reference's key and proof scripts (dizkus-scripts/4_gen_vkey.sh:10, 5_gen_proof.sh:17,
+ * circuit/scripts/verify_proof_groth16.sh:2):
+ *   node cli.js zkey export verificationkey <circuit.zkey> [verification_key.json]
+ *   node cli.js groth16 verify <verification_key.json> <public.json> <proof.json>
  */
 const fs = require('fs');
 const { groth16, zKey, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, preparePhase2, powersOfTau, wtns: wtnsApi, release } = require('./groth16');
 
 const USAGE = 'usage: cli.js groth16 prove <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n' +
+              '       cli.js groth16 verify <verification_key.json> <public.json> <proof.json>\n' +
+              '       cli.js zkey export verificationkey <circuit.zkey> [verification_key.json]\n' +
               '       cli.js zkey export soliditycalldata <public.json> <proof.json>\n' +
               '       cli.js groth16 setup|zkey new <circuit.r1cs> <pot.ptau> <circuit_0000.zkey>\n' +
               '       cli.js zkey contribute <in.zkey> <out.zkey> -e=<entropy> [-n=name]\n' +
@@ -61,6 +67,23 @@ async function main(argv) {
     const proof = JSON.parse(fs.readFileSync(argv[4], 'utf-8'));
     process.stdout.write(await exportSolidityCallData(proof, pub) + '\n');
     return 0;
+  }
+  if ((argv.length === 4 || argv.length === 5) && argv[0] === 'zkey' && argv[1] === 'export' && argv[2] === 'verificationkey') {
+    const vKey = await zKey.exportVerificationKey(argv[3]);
+    fs.writeFileSync(argv[4] || 'verification_key.json', JSON.stringify(vKey, null, 1), 'utf-8');
+    return 0;
+  }
+  if (argv.length === 5 && argv[0] === 'groth16' && argv[1] === 'verify') {
+    // snarkjs' log lines (recalled, unpinned): "[INFO]  snarkJS: OK!" and exit 0, else "[ERROR] snarkJS: Invalid
+    // proof" and exit 1
+    const logger = {
+      info: (m) => process.stdout.write(`[INFO]  snarkJS: ${m}\n`),
+      error: (m) => process.stdout.write(`[ERROR] snarkJS: ${m}\n`),
+    };
+    const vKey = JSON.parse(fs.readFileSync(argv[2], 'utf-8'));
+    const pub = JSON.parse(fs.readFileSync(argv[3], 'utf-8'));
+    const proof = JSON.parse(fs.readFileSync(argv[4], 'utf-8'));
+    return (await groth16.verify(vKey, pub, proof, logger)) ? 0 : 1;
   }
   const setupArgs = argv.filter((a) => !a.startsWith('-e='));  // entropy: unused by `groth16 setup`
   if (setupArgs.length === 5 && ((argv[0] === 'zkey' && argv[1] === 'new') || (argv[0] === 'groth16' && argv[1] === 'setup'))) {

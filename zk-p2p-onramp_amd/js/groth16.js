@@ -452,6 +452,57 @@ async function importBellman(zkeyNameOld, mpcparamsName, zkeyNameNew, name, logg
   return out;
 }
 
+/*
+ * snarkjs' `zKey.exportVerificationKey(zkeyName)` (the `zkey export verificationkey` step): the verification key
+ * object of a key's sections 2 and 3, vk_alphabeta_12 by the host pairing.  Host only.
+ */
+async function exportVerificationKey(zkeyName, logger) {
+  const vKey = JSON.parse(addon.zkeyExportVkey(readInput(zkeyName)));
+  if (logger && logger.info) logger.info(`zkey export verificationkey: nPublic ${vKey.nPublic}`);
+  return vKey;
+}
+
+function proofBytes(proof) {
+  const b = Buffer.alloc(256);
+  const put = (v, at) => toBuf32(v).copy(b, at);
+  put(proof.pi_a[0], 0); put(proof.pi_a[1], 32);
+  put(proof.pi_b[0][0], 64); put(proof.pi_b[0][1], 96); put(proof.pi_b[1][0], 128); put(proof.pi_b[1][1], 160);
+  put(proof.pi_c[0], 192); put(proof.pi_c[1], 224);
+  return b;
+}
+
+/*
+ * `groth16.verifyBatch(vkey, [{publicSignals, proof}], logger)`: snarkjs' verification of many proofs under one
+ * verification key in one call, the per-proof Miller loops on the GPU; resolves to one boolean per proof.  A value
+ * that does not fit 256 bits or a publicSignals of another length than the key's nPublic rejects, as a caller error.
+ */
+async function verifyBatch(vkey, items, logger, device) {
+  const vKey = typeof vkey === 'string' ? JSON.parse(vkey) : vkey;
+  const nPublic = vKey.nPublic;
+  for (const it of items) {
+    if (it.publicSignals.length !== nPublic) throw new Error('Invalid number of public signals');
+  }
+  const proofs = Buffer.concat(items.map((it) => proofBytes(it.proof)));
+  const pubs = Buffer.concat(items.map((it) => Buffer.concat(it.publicSignals.map((s) => toBuf32(s)))));
+  const verdict = addon.groth16VerifyBatch(JSON.stringify(vKey), proofs, pubs, nPublic, device || 0);
+  const res = Array.from(verdict, (x) => x !== 0);
+  if (logger && logger.info) logger.info(`groth16 verify: ${res.filter((x) => x).length} of ${res.length} valid`);
+  return res;
+}
+
+/*
+ * snarkjs' `groth16.verify(vk_verifier, publicSignals, proof, logger)`: resolves to true and logs "OK!" (info), or
+ * to false and logs "Invalid proof" (error) -- the words as recalled from snarkjs, unpinned.
+ */
+async function verify(vkey, publicSignals, proof, logger, device) {
+  const [ok] = await verifyBatch(vkey, [{ publicSignals, proof }], undefined, device);
+  if (logger) {
+    if (ok && logger.info) logger.info('OK!');
+    if (!ok && logger.error) logger.error('Invalid proof');
+  }
+  return ok;
+}
+
 function release() {
   for (const h of provers.values()) addon.freeProver(h);
   for (const h of memProvers.values()) addon.freeProver(h);
@@ -460,9 +511,9 @@ function release() {
 }
 
 module.exports = {
-  groth16: { prove, proveBatch },
+  groth16: { prove, proveBatch, verify, verifyBatch },
   proveBatch,
-  zKey: { exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit, exportBellman,
+  zKey: { exportVerificationKey, exportSolidityCallData, newZKey, beacon, contribute, verifyFromR1cs, verifyFromInit, exportBellman,
           bellmanContribute, importBellman },
   powersOfTau: { newAccumulator, contribute: contributePtau, beacon: beaconPtau, preparePhase2, verify: verifyPtau,
                  exportChallenge, challengeContribute, importResponse },

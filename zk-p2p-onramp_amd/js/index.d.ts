@@ -17,12 +17,21 @@ export declare const groth16: {
   // one entry per witness: the proof, or an Error (code = zkp_status) for a witness that failed
   proveBatch(zkeyFileName: Input, witnesses: Input[], logger?: Logger, opts?: BatchOptions):
     Promise<({ proof: Proof; publicSignals: string[] } | Error)[]>;
+  /** snarkjs' `groth16.verify(vKey, publicSignals, proof, logger)` from a verification key, the Miller loop on the
+   *  GPU: logs "OK!" (info) or "Invalid proof" (error).  A malformed key rejects. */
+  verify(vkey: VerificationKey | string, publicSignals: string[], proof: Proof, logger?: VerifyLogger,
+         device?: number): Promise<boolean>;
+  /** many proofs under one key in one call: one verdict per proof */
+  verifyBatch(vkey: VerificationKey | string, items: { publicSignals: string[]; proof: Proof }[], logger?: Logger,
+              device?: number): Promise<boolean[]>;
 };
 export declare function proveBatch(zkey: Input, witnesses: Input[], logger?: Logger, opts?: BatchOptions):
   Promise<({ proof: Proof; publicSignals: string[] } | Error)[]>;
 export declare function prove(zkey: Input, wtns: Input, logger?: Logger, opts?: ProveOptions):
   Promise<{ proof: Proof; publicSignals: string[] }>;
 export declare const zKey: {
+  /** snarkjs' `zKey.exportVerificationKey(zkeyName)` (`zkey export verificationkey`); host only */
+  exportVerificationKey(zkeyName: Input, logger?: Logger): Promise<VerificationKey>;
   exportSolidityCallData(proof: Proof, publicSignals: string[]): Promise<string>;
   /** `snarkjs zkey new` on the GPU; writes zkeyName when given, returns the key bytes */
   newZKey(r1csName: Input, ptauName: Input, zkeyName?: string | { type: "mem"; data?: Uint8Array }, logger?: Logger,
@@ -110,5 +119,17 @@ export declare function verifyFromInit(initName: Input, zkeyName: Input, logger?
 export declare function exportSolidityCallData(proof: Proof, publicSignals: string[]): Promise<string>;
 export declare function onRampArgs(proof: Proof, publicSignals: string[]):
   [[string, string], [[string, string], [string, string]], [string, string], string[]];
+/** snarkjs' verification_key.json object (`zkey export verificationkey`). */
+export interface VerificationKey {
+  protocol: "groth16";
+  curve: "bn128";
+  nPublic: number;
+  vk_alpha_1: string[];
+  vk_beta_2: string[][];
+  vk_gamma_2: string[][];
+  vk_delta_2: string[][];
+  vk_alphabeta_12?: string[][][];
+  IC: string[][];
+}
 export declare function release(): void;
 export declare function version(): string;

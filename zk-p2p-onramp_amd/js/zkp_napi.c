@@ -1000,6 +1000,87 @@ static napi_value js_prove_batch(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* zkeyExportVkey(zkeyBuffer) -> string: `snarkjs zkey export verificationkey` (zkp_zkey_export_vkey), host only */
+static napi_value js_zkey_export_vkey(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b0 = false;
+  if (argc >= 1) napi_is_buffer(env, argv[0], &b0);
+  if (!b0) {
+    napi_throw_type_error(env, NULL, "zkeyExportVkey(zkeyBuffer)");
+    return NULL;
+  }
+  void* zkey;
+  size_t zkey_len, need = 0;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[0], &zkey, &zkey_len));
+  zkp_status st = zkp_zkey_export_vkey((const uint8_t*)zkey, zkey_len, NULL, 0, &need);
+  if (st != ZKP_OK) return throw_status(env, st);
+  char* text = (char*)malloc(need);
+  if (!text) return throw_status(env, ZKP_ERR_OUT_OF_MEMORY);
+  st = zkp_zkey_export_vkey((const uint8_t*)zkey, zkey_len, text, need, NULL);
+  napi_value out = NULL;
+  if (st == ZKP_OK && napi_create_string_utf8(env, text, need - 1, &out) != napi_ok) out = NULL;
+  free(text);
+  if (st != ZKP_OK) return throw_status(env, st);
+  if (!out) napi_throw_error(env, NULL, "N-API call failed: napi_create_string_utf8");
+  return out;
+}
+
+/* groth16VerifyBatch(vkeyJsonString, proofsBuffer, publicBuffer, nPublic, device?) -> Buffer of n verdict bytes:
+ * `snarkjs groth16 verify` of n proofs under one key (zkp_verifier_*), synchronous.  proofsBuffer: n x 256 bytes
+ * (pi_a x, y; pi_b x.c0, x.c1, y.c0, y.c1; pi_c x, y: 32-byte LE each), publicBuffer: n x nPublic x 32 bytes LE.
+ * An invalid proof is a 0 byte; a malformed key or an nPublic other than the key's throws. */
+static napi_value js_groth16_verify_batch(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bool b1 = false, b2 = false;
+  if (argc >= 4) napi_is_buffer(env, argv[1], &b1), napi_is_buffer(env, argv[2], &b2);
+  size_t json_len = 0;
+  if (!b1 || !b2 || napi_get_value_string_utf8(env, argv[0], NULL, 0, &json_len) != napi_ok) {
+    napi_throw_type_error(env, NULL, "groth16VerifyBatch(vkeyJsonString, proofsBuffer, publicBuffer, nPublic, device?)");
+    return NULL;
+  }
+  uint32_t n_public = 0;
+  int device = 0;
+  napi_get_value_uint32(env, argv[3], &n_public);
+  if (argc > 4) napi_get_value_int32(env, argv[4], &device);
+  void *pp, *sp;
+  size_t plen, slen;
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &pp, &plen));
+  NAPI_CALL(env, napi_get_buffer_info(env, argv[2], &sp, &slen));
+  const size_t n = plen / 256;
+  if (plen % 256 || slen != n * (size_t)n_public * 32) {
+    napi_throw_type_error(env, NULL, "groth16VerifyBatch: proofsBuffer is n x 256 bytes, publicBuffer n x nPublic x 32");
+    return NULL;
+  }
+  char* json = (char*)malloc(json_len + 1);
+  zkp_proof* proofs = (zkp_proof*)calloc(n ? n : 1, sizeof(zkp_proof));
+  napi_value out = NULL;
+  void* verdict = NULL;
+  zkp_verifier* v = NULL;
+  zkp_status st = ZKP_ERR_OUT_OF_MEMORY;
+  if (json && proofs && napi_get_value_string_utf8(env, argv[0], json, json_len + 1, &json_len) == napi_ok &&
+      napi_create_buffer(env, n, &verdict, &out) == napi_ok) {
+    for (size_t i = 0; i < n; ++i) {
+      const uint8_t* b = (const uint8_t*)pp + 256 * i;
+      memcpy(proofs[i].pi_a, b, 64);
+      memcpy(proofs[i].pi_b, b + 64, 128);
+      memcpy(proofs[i].pi_c, b + 192, 64);
+      proofs[i].n_public = proofs[i].public_capacity = n_public;
+      proofs[i].public_signals = (uint8_t*)sp + (size_t)n_public * 32 * i;
+    }
+    st = zkp_verifier_load_vkey_json(device, json, json_len, &v);
+    if (st == ZKP_OK) st = zkp_verifier_verify(v, proofs, n, NULL, (uint8_t*)verdict, NULL);
+  }
+  zkp_verifier_free(v);
+  free(proofs);
+  free(json);
+  if (st != ZKP_OK) return throw_status(env, st);
+  return out;
+}
+
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"version", NULL, js_version, NULL, NULL, NULL, napi_default, NULL},
@@ -1024,6 +1105,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"zkeyExportBellman", NULL, js_zkey_export_bellman, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyBellmanContribute", NULL, js_zkey_bellman_contribute, NULL, NULL, NULL, napi_default, NULL},
       {"zkeyImportBellman", NULL, js_zkey_import_bellman, NULL, NULL, NULL, napi_default, NULL},
+      {"zkeyExportVkey", NULL, js_zkey_export_vkey, NULL, NULL, NULL, napi_default, NULL},
+      {"groth16VerifyBatch", NULL, js_groth16_verify_batch, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

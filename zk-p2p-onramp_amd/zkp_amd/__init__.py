@@ -251,6 +251,22 @@ def load_library(path: str = LIB_PATH):
                      "zkp_quotient_part_staged", "zkp_prove_partial_ext_staged"):
             if hasattr(lib, name):
                 getattr(lib, name).restype = ctypes.c_int
+        if hasattr(lib, "zkp_verifier_verify"):
+            lib.zkp_zkey_export_vkey.argtypes = [u8p, sz, ctypes.c_char_p, sz, ctypes.POINTER(sz)]
+            lib.zkp_verifier_load_vkey_json.argtypes = [ctypes.c_int, ctypes.c_char_p, sz, ctypes.POINTER(P)]
+            lib.zkp_verifier_load_zkey.argtypes = [ctypes.c_int, u8p, sz, ctypes.POINTER(P)]
+            lib.zkp_verifier_info.argtypes = [P, ctypes.POINTER(ctypes.c_uint32)]
+            lib.zkp_verifier_verify.argtypes = [P, ctypes.POINTER(_Proof), sz, u8p, u8p, ctypes.POINTER(sz)]
+            lib.zkp_verifier_timings.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+            lib.zkp_verifier_free.argtypes = [P]
+            lib.zkp_verifier_free.restype = None
+            lib.zkp_miller_loop.argtypes = [ctypes.c_int, u8p, u8p, sz, u8p]
+            lib.zkp_final_exponentiation.argtypes = [u8p, u8p]
+            lib.zkp_fq12_product.argtypes = [ctypes.c_int, u8p, sz, u8p]
+            for name in ("zkp_zkey_export_vkey", "zkp_verifier_load_vkey_json", "zkp_verifier_load_zkey",
+                         "zkp_verifier_info", "zkp_verifier_verify", "zkp_verifier_timings", "zkp_miller_loop",
+                         "zkp_final_exponentiation", "zkp_fq12_product"):
+                getattr(lib, name).restype = ctypes.c_int
         _lib = lib
         return lib
 
@@ -1285,6 +1301,150 @@ def pairing(g1, g2):
     raw = bytes(out)
     v = [_le(raw[32 * i:32 * i + 32]) for i in range(12)]
     return [[(v[6 * h + 2 * k], v[6 * h + 2 * k + 1]) for k in range(3)] for h in range(2)]
+
+
+def _f12_nested(raw: bytes):
+    v = [_le(raw[32 * i:32 * i + 32]) for i in range(12)]
+    return [[(v[6 * h + 2 * k], v[6 * h + 2 * k + 1]) for k in range(3)] for h in range(2)]
+
+
+def _f12_bytes(f) -> bytes:
+    return b"".join(int(c).to_bytes(32, "little") for h in f for k in h for c in k)
+
+
+def _g1_bytes(p) -> bytes:
+    return bytes(64) if p is None else b"".join(int(v).to_bytes(32, "little") for v in p)
+
+
+def _g2_bytes(q) -> bytes:
+    return bytes(128) if q is None else b"".join(int(v).to_bytes(32, "little")
+                                                 for v in (q[0][0], q[0][1], q[1][0], q[1][1]))
+
+
+def miller_loop(pairs, device: int = 0):
+    """The device Miller loop (zkp_miller_loop) of every (P, Q) of `pairs`, points as `pairing` takes them.
+    Each value equals the host's Miller value only up to a factor that the final exponentiation removes:
+    final_exponentiation(miller_loop([(P, Q)])[0]) == pairing(P, Q)."""
+    pairs = list(pairs)
+    n = len(pairs)
+    gp, gk = _buf(b"".join(_g1_bytes(p) for p, _ in pairs) or bytes(1))
+    qp, qk = _buf(b"".join(_g2_bytes(q) for _, q in pairs) or bytes(1))
+    out = (ctypes.c_uint8 * max(384 * n, 1))()
+    _check(load_library().zkp_miller_loop(device, gp, qp, n, ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8))))
+    raw = bytes(out)
+    return [_f12_nested(raw[384 * i:384 * i + 384]) for i in range(n)]
+
+
+def final_exponentiation(f):
+    """Host final exponentiation (zkp_final_exponentiation) of an Fq12 value in `pairing`'s nesting."""
+    ip, ik = _buf(_f12_bytes(f))
+    out = (ctypes.c_uint8 * 384)()
+    _check(load_library().zkp_final_exponentiation(ip, ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8))))
+    return _f12_nested(bytes(out))
+
+
+def fq12_product(values, device: int = 0):
+    """Product of Fq12 values by the device reduction kernel (zkp_fq12_product); [] gives 1."""
+    values = list(values)
+    ip, ik = _buf(b"".join(_f12_bytes(f) for f in values) or bytes(1))
+    out = (ctypes.c_uint8 * 384)()
+    _check(load_library().zkp_fq12_product(device, ip, len(values), ctypes.cast(out, ctypes.POINTER(ctypes.c_uint8))))
+    return _f12_nested(bytes(out))
+
+
+def export_verification_key_text(zkey) -> str:
+    """`snarkjs zkey export verificationkey`: the JSON text (zkp_zkey_export_vkey)."""
+    lib = load_library()
+    zp, zk = _buf(zkey)
+    need = ctypes.c_size_t()
+    _check(lib.zkp_zkey_export_vkey(zp, len(zkey), None, 0, ctypes.byref(need)))
+    buf = ctypes.create_string_buffer(need.value)
+    _check(lib.zkp_zkey_export_vkey(zp, len(zkey), buf, need.value, ctypes.byref(need)))
+    return buf.value.decode()
+
+
+def export_verification_key(zkey) -> dict:
+    """`snarkjs zkey export verificationkey` as the parsed object."""
+    import json
+    return json.loads(export_verification_key_text(zkey))
+
+
+def _proof_tuple(proof):
+    """snarkjs' proof object (pi_a / pi_b / pi_c decimal strings) or the ((ax, ay), ((bx0, bx1), (by0, by1)),
+    (cx, cy)) tuple -> the tuple"""
+    if isinstance(proof, dict):
+        a, b, c = proof["pi_a"], proof["pi_b"], proof["pi_c"]
+        return ((int(a[0]), int(a[1])), ((int(b[0][0]), int(b[0][1])), (int(b[1][0]), int(b[1][1]))),
+                (int(c[0]), int(c[1])))
+    return proof
+
+
+class Verifier:
+    """`snarkjs groth16 verify` from a verification key, batched, with the per-proof Miller loops on the GPU
+    (zkp_verifier_*).  vkey_or_zkey: the verification key as a dict, its JSON text (str), or the bytes of a
+    .zkey (the key of its sections 2 and 3)."""
+
+    def __init__(self, vkey_or_zkey, device: int = 0):
+        import json
+        lib = load_library()
+        self._lib = lib
+        self._h = ctypes.c_void_p()
+        if isinstance(vkey_or_zkey, dict):
+            vkey_or_zkey = json.dumps(vkey_or_zkey)
+        if isinstance(vkey_or_zkey, str):
+            text = vkey_or_zkey.encode()
+            _check(lib.zkp_verifier_load_vkey_json(device, text, len(text), ctypes.byref(self._h)))
+        else:
+            zp, zk = _buf(vkey_or_zkey)
+            _check(lib.zkp_verifier_load_zkey(device, zp, len(vkey_or_zkey), ctypes.byref(self._h)))
+        n = ctypes.c_uint32()
+        _check(lib.zkp_verifier_info(self._h, ctypes.byref(n)))
+        self.n_public = n.value
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.zkp_verifier_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def verify_batch(self, items, seed=None):
+        """items: (proof, public_signals) pairs -> one bool each.  seed: 32 bytes for tests; None (what a
+        production call passes) draws it from the OS CSPRNG."""
+        items = list(items)
+        n = len(items)
+        arr = (_Proof * max(n, 1))()
+        keep = []
+        for i, (proof, pub) in enumerate(items):
+            pr, pbuf = _proof_struct(_proof_tuple(proof), [int(x) for x in pub])
+            keep.append(pbuf)
+            ctypes.memmove(ctypes.byref(arr, i * ctypes.sizeof(_Proof)), ctypes.byref(pr), ctypes.sizeof(_Proof))
+        valid = (ctypes.c_uint8 * max(n, 1))()
+        n_valid = ctypes.c_size_t()
+        sp = None
+        if seed is not None:
+            if len(seed) != 32:
+                raise ValueError("seed: 32 bytes")
+            sp, sk = _buf(bytes(seed))
+        _check(self._lib.zkp_verifier_verify(self._h, arr, n, sp, ctypes.cast(valid, ctypes.POINTER(ctypes.c_uint8)),
+                                             ctypes.byref(n_valid)))
+        out = [bool(valid[i]) for i in range(n)]
+        assert n_valid.value == sum(out)
+        return out
+
+    def verify(self, proof, public_signals) -> bool:
+        return self.verify_batch([(proof, public_signals)])[0]
+
+    def timings(self) -> dict:
+        ms = (ctypes.c_double * 9)()
+        _check(self._lib.zkp_verifier_timings(ms, 9))
+        keys = ("gates_ms", "scalar_ms", "miller_ms", "product_ms", "host_miller_ms", "final_exp_ms", "search_ms",
+                "total_ms", "node_checks")
+        return dict(zip(keys, list(ms)))
 
 
 def solidity_calldata(proof, public_signals) -> str:
